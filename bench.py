@@ -3,6 +3,7 @@
 
   python bench.py --gpus N --steps K --warmup W      N > 1 without a torchrun environment: bench.py re-executes itself
                                                      under torch.distributed.run with N ranks (one per GPU, RCCL)
+  python bench.py ... --dump-outputs DIR              also write what the last timed step computed as DIR/<name>.npy
 
 A "step" = one whole pass of the hot path over one batch of synthetic frames, raw points resident in HBM ->
 voxelize -> 7 rulebooks -> 14 sparse convs -> densify -> BEVNet -> heads -> anchors mask -> decode/filter -> PSWarp
@@ -167,6 +168,27 @@ def synth_gt_on_points(cloud, seed, n=8, config="car"):
     return b
 
 
+def frame_outputs(results):
+    """InferencePlan.results() -- per frame (boxes [k,7], scores [k], labels [k]) or Nones when nothing was detected -- as
+    named float32 arrays (no detections: empty arrays of the same shapes)."""
+    out = {}
+    for j, (boxes, scores, labels) in enumerate(results):
+        out["frame%d_boxes" % j] = np.zeros((0, 7), np.float32) if boxes is None else boxes
+        out["frame%d_scores" % j] = np.zeros((0,), np.float32) if scores is None else scores
+        out["frame%d_labels" % j] = np.zeros((0,), np.float32) if labels is None else labels
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in out.items()}
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 / float64 only, 64 MB at most in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, "outputs to dump are %d bytes (> 64 MB)" % total
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+
+
 def csrc_hash():
     from sassd import _C
     return _C.csrc_hash()
@@ -186,19 +208,19 @@ def stamped_traffic(fname):
 
 
 def train_measure(args, dev, rank, world, config="car", precision="bf16", steps=40, warmup=8, batch=0, frames=16,
-                  fused_bn=None):
+                  fused_bn=None, dump_dir=None):
     """_train_measure with the process-wide training switches (BEV precision, fused sparse BatchNorm) restored afterwards,
     whatever happens inside: the inference half of the default line runs in the same process."""
     from sassd import autograd as AG, spconv as SP
     prev = (AG.bev_precision(), SP.SparseSequential.fuse_bn_relu)
     try:
-        return _train_measure(args, dev, rank, world, config, precision, steps, warmup, batch, frames, fused_bn)
+        return _train_measure(args, dev, rank, world, config, precision, steps, warmup, batch, frames, fused_bn, dump_dir)
     finally:
         AG.set_bev_precision(prev[0])
         SP.SparseSequential.fuse_bn_relu = prev[1]
 
 
-def _train_measure(args, dev, rank, world, config, precision, steps, warmup, batch, frames, fused_bn):
+def _train_measure(args, dev, rank, world, config, precision, steps, warmup, batch, frames, fused_bn, dump_dir=None):
     """The training half of the BASELINE metric.  config "car": BASELINE configs[2] (car_cfg training, batch 2 / GPU,
     bf16 MFMA operands in the BEV convs); "waymo": configs[4] (180k-point frames, 0.1 m voxels, batch 4 / GPU).
     A step = device voxelize + anchor masks + rulebooks (side stream) + forward_train + backward + bucketed gradient
@@ -216,7 +238,9 @@ def _train_measure(args, dev, rank, world, config, precision, steps, warmup, bat
     anchors = dict(Car=torch.from_numpy(w["anchors"]).to(dev))
     anchors_bv = dict(Car=torch.from_numpy(w["anchors_bv"]).to(dev))
     opt = train.build_optimizer(model, cfg.optimizer, world)
-    sched = train.build_scheduler(opt, 5 * steps + warmup, 1, cfg.optimizer, cfg.lr_config)   # (up to five trials)
+    # (the one-cycle schedule keeps the length it was laid out for when short runs were repeated five times: every step
+    # computes the same update as before)
+    sched = train.build_scheduler(opt, 5 * steps + warmup, 1, cfg.optimizer, cfg.lr_config)
     sync = train.GradSync(opt.flat, time_comm=True, force=getattr(args, "force_ddp", False))
     nf = max(min(frames, 8) if config == "waymo" else frames, B)
     host = [w["frame"](rank * 1000 + i) for i in range(nf)]
@@ -250,29 +274,19 @@ def _train_measure(args, dev, rank, world, config, precision, steps, warmup, bat
     for i in range(warmup):
         loss, _ = one(i)
     comm = []
-    it0 = [warmup]
-
-    def trial():                                        # EXACTLY `steps` steps between barrier + synchronize
-        barrier()
-        t0 = time.perf_counter()
-        last = None
-        for i in range(steps):
-            last = one(it0[0] + i)
-            if sync.on and i >= steps - 5:
-                comm.append(sync.comm_ms())             # (synchronises on the exchange's end event: last steps only)
-        torch.cuda.synchronize()
-        dl = time.perf_counter() - t0
-        barrier()
-        it0[0] += steps
-        return D.allreduce_max(time.perf_counter() - t0, dev), dl, last
-
-    trials = [trial()]
-    if trials[0][0] < 0.5:                              # short run (40 steps = 0.35 s): five trials, the median reported
-        trials += [trial() for _ in range(4)]
-    trials_dt = sorted(t[0] for t in trials)
-    dt = trials_dt[len(trials_dt) // 2]
-    dt_local = sorted(t[1] for t in trials)[len(trials) // 2]
-    loss, terms = trials[-1][2]
+    barrier()                                           # EXACTLY `steps` steps between barrier + synchronize
+    t0 = time.perf_counter()
+    for i in range(steps):
+        loss, terms = one(warmup + i)
+        if sync.on and i >= steps - 5:
+            comm.append(sync.comm_ms())                 # (synchronises on the exchange's end event: last steps only)
+    torch.cuda.synchronize()
+    dt_local = time.perf_counter() - t0
+    barrier()
+    dt = D.allreduce_max(time.perf_counter() - t0, dev)
+    if dump_dir and rank == 0:                          # the last timed step's loss and terms, as its caller receives them
+        dump_outputs(dump_dir, dict({"loss": np.array(float(loss), np.float64)},
+                                    **{"term_" + k: np.array(float(v), np.float64) for k, v in terms.items()}))
     per_rank = D.allgather_float(dt_local / steps * 1e3, dev) if world > 1 else [dt_local / steps * 1e3]
     voxels = int(sum(v.shape[0] for v in state["batch"]["voxels"]))
     # dominant kernel of the training step, timed live with events on the launch stream: the 3x3 BEV conv (14 launches
@@ -326,8 +340,6 @@ def _train_measure(args, dev, rank, world, config, precision, steps, warmup, bat
         "metric": "%s training samples/sec (whole job)" % ("KITTI-Car" if config == "car" else "Waymo-scale synthetic"),
         "value": round(sps, 3), "unit": "samples/s",
         "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(dt / steps * 1e3, 3),
-        "trials": {"n": len(trials_dt), "steps_each": steps, "reported": "median",
-                   "ms_per_step_min": round(trials_dt[0] / steps * 1e3, 3), "ms_per_step_max": round(trials_dt[-1] / steps * 1e3, 3)},
         "ms_per_step_per_rank": [round(v, 3) for v in per_rank],
         "allreduce_ms": None if not comm else round(float(np.mean([c for c in comm if c is not None])), 3),
         "allreduce_note": "first gradient-bucket launch -> last bucket complete on the compute stream (4 buckets launched "
@@ -339,9 +351,9 @@ def _train_measure(args, dev, rank, world, config, precision, steps, warmup, bat
                                   (world, "; one-rank communicator forced" if (sync.on and world == 1) else "")},
         "roofline": roof,
         "final_loss": round(float(loss), 4), "loss_terms": {k: round(float(v), 4) for k, v in terms.items()},
-        "final_loss_note": "after %d steps of a one-cycle schedule laid out for %d (warm-up + up to five trials): a sanity value "
+        "final_loss_note": "after %d steps of a one-cycle schedule laid out for %d (5 x steps + warm-up): a sanity value "
                            "(finite, six non-zero terms), not comparable across --steps or with rounds 1-3, whose schedule "
-                           "was sized for one trial" % (warmup + len(trials_dt) * steps, 5 * steps + warmup)}
+                           "was sized for one trial" % (warmup + steps, 5 * steps + warmup)}
 
 
 def main_train(args):
@@ -355,7 +367,7 @@ def main_train(args):
         K0.DEFAULT_CFG["spconv"] = K0.spconv_cfg(args.spconv_cfg)     # host-side default of the binding, passed per call
     out = train_measure(args, dev, rank, world, "waymo" if args.config == "waymo" else "car", args.precision,
                         args.steps, args.warmup, args.batch if args.batch > 1 else 0, args.frames,
-                        False if args.torch_bn else None)
+                        False if args.torch_bn else None, dump_dir=args.dump_outputs)
     if rank == 0:
         print(json.dumps(out))
 
@@ -486,7 +498,7 @@ def main():
     ap.add_argument("--force-ddp", action="store_true", help="N = 1: initialise a ONE-RANK nccl (RCCL) communicator and run the "
                     "training step's bucketed gradient all-reduce through it (hook-launched async collectives on the HIP "
                     "stream), so that `train.allreduce_ms` is measured on a single-GPU box")
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (exactly this many; ms_per_step = their time / steps)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train", action="store_true", help="default (car) run: skip the `train` record (BASELINE "
@@ -520,7 +532,14 @@ def main():
                     "rulebooks / anchor masks in front of the feature path on the frame's own stream")
     ap.add_argument("--no-extra", action="store_true", help="default (car) run: skip the `infer_multi` / `infer_waymo` / "
                     "`train_waymo` records (BASELINE configs[3] / [4]) that follow the headline measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last one "
+                    "returned to its caller as DIR/<name>.npy: inference -- the detections of every frame of the step on "
+                    "rank 0 (frame<j>_boxes [k,7], frame<j>_scores [k], frame<j>_labels [k]; float32); --mode train -- the "
+                    "loss and its terms (loss, term_<name>; float64).  Inputs and weights are seeded: the same arguments "
+                    "give the same inputs on every run")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     env_world = int(os.environ.get("WORLD_SIZE", "0") or 0)
     if args.gpus > 1 and env_world == 0:
         respawn_under_torchrun(args)                     # does not return
@@ -590,25 +609,19 @@ def main():
         st = int(pl.status.item())
         assert st == 0, "pipeline status 0x%x" % st
 
-    # EXACTLY K steps between barrier + synchronize on both sides, max over ranks.  A trial shorter than half a second
-    # (the driver's 20 steps are 30 ms) is repeated -- five trials at least, each of them K steps bracketed the same
-    # way -- and the MEDIAN trial is reported; `steps` / `ms_per_step` keep their meaning, `trials` lists the spread.
-    def trial():
-        barrier()
-        t0 = time.perf_counter()
-        for i in range(args.steps):
-            step(i)
-        barrier()
-        return D.allreduce_max(time.perf_counter() - t0, dev)
-
-    trial_dts = [trial()]
-    if trial_dts[0] < 0.5:
-        ntr = int(D.allreduce_max(float(max(5, min(25, int(np.ceil(1.5 / max(trial_dts[0], 1e-4)))))), dev))
-        trial_dts += [trial() for _ in range(ntr - 1)]
-    dt = float(np.median(trial_dts))
+    # EXACTLY K = --steps timed steps between barrier + synchronize on both sides, max over ranks: the run is K steps long,
+    # so a caller that wants a longer (less noisy) measurement asks for more steps
+    barrier()
+    t0 = time.perf_counter()
+    for i in range(args.steps):
+        step(i)
+    barrier()
+    dt = D.allreduce_max(time.perf_counter() - t0, dev)
+    if args.dump_outputs and rank == 0:                  # what the last timed step handed its caller (before any other work)
+        dump_outputs(args.dump_outputs, frame_outputs(plans[(args.steps - 1) % S].results()))
     for pi, pl in enumerate(plans):
         st = int(pl.status.item())
-        assert st == 0, "pipeline status 0x%x on plan %d after the timed trials" % (st, pi)
+        assert st == 0, "pipeline status 0x%x on plan %d after the timed steps" % (st, pi)
     ndet = int(plan.det["counts"].sum().item())
     ncand = int(plan.df["counts"].sum().item())
     fps = args.steps * B * world / dt
@@ -766,9 +779,6 @@ def main():
                   "%s inference frames/sec (whole job)" % args.config,
         "value": round(fps, 3), "unit": "frames/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
-        "trials": {"n": len(trial_dts), "steps_each": args.steps, "reported": "median",
-                   "ms_per_step_min": round(min(trial_dts) / args.steps * 1e3, 4),
-                   "ms_per_step_max": round(max(trial_dts) / args.steps * 1e3, 4)},
         "higher_is_better": True, "scaling": "weak",
         "vs_baseline": round(fps / world / PUBLISHED_FPS, 3) if headline else None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": "%s, batch=%d, random-init SA-SSD weights, points resident in HBM" % (w["desc"], B),
