@@ -186,6 +186,12 @@ int sassd_spconv_bwd_weight(const float *x, const float *dy, const int32_t *nbr,
  * channel_order 0: channel = c*D + d (reference); 1: channel = d*C + c (internal, conv0 weights permuted). */
 int sassd_densify(const float *feats, const int32_t *indices, const int32_t *n_ptr, int cap, int C,
                   int D, int H, int W, int batch_size, int channel_order, float *out, void *stream);
+/* The same map as bf16 (each feature rounded to nearest even: the operand BEV conv0 rounds) for InferencePlan(precision="bf16"):
+ * out [B, C*D, H, W] bf16, 16-byte aligned, cleared by a fill kernel (never hipMemsetAsync: no memset node in a captured frame).
+ * Supported: H*W % 8 == 0; else SASSD_EINVAL before any launch. */
+int sassd_densify_bf16_supported(int C, int D, int H, int W);
+int sassd_densify_bf16(const float *feats, const int32_t *indices, const int32_t *n_ptr, int cap, int C, int D, int H, int W,
+                       int batch_size, int channel_order, void *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * (a9,a10,a12) Dense 2-D convolution (3x3 pad 1 or 1x1), NCHW fp32, on fp32 MFMA (v_mfma_f32_32x32x2_f32),
@@ -324,6 +330,29 @@ size_t sassd_conv1x1_bf16_packed_elems(int Cin, int Cout);
 int sassd_conv1x1_bf16_pack_weight(const float *w, int Cout, int Cin, int transposed, void *packed, void *stream);
 int sassd_conv1x1_bf16_fwd(const float *x, const void *w_packed, const float *shift, float *y, int batch, int Cin, int Cout,
                            int HW, void *stream);
+
+/* bf16 inference (InferencePlan(precision="bf16")): every dense conv of the frame on bf16 operands with fp32 accumulation.
+ * x is a bf16 NCHW map (rounded by its producer: rounding at the store gives the operand rounding at the load would), the
+ * weights are the RAW conv weights rounded once at pack time (BatchNorm is not folded into them), and the epilogue applies the
+ * eval BatchNorm + ReLU in fp32 to the accumulator -- relu(acc * scale[co] + shift[co]) (relu = 0: no ReLU; scale = NULL:
+ * acc + shift[co], shift may be NULL too) -- and stores bf16 (y_bf16 = 1: the map of the next conv, rounded to nearest even)
+ * or fp32.  Caller-owned buffers, no allocation, no host sync; SASSD_EINVAL on NULL pointers, misalignment or unsupported
+ * shapes before anything touches the device.
+ * 3x3 pad 1 (BEV conv0-conv6, the part-sensitive 256 -> 28 conv): the implicit GEMM of sassd_conv2d_bf16_fwd with a bf16
+ * loader.  Weights [Cout,Cin,3,3] fp32 packed at Cout rounded up to 32 (zero rows; sassd_conv2d_bf16_infer_packed_elems 16-bit
+ * elements); y [B,Cout,H,W] holds only the Cout real maps.  Supported: W >= 16, W % 4 == 0.  x 8-byte, the pack 16-byte,
+ * y 8-byte (bf16) / 16-byte (fp32) aligned. */
+int sassd_conv2d_bf16_infer_supported(int Cin, int Cout, int H, int W);
+size_t sassd_conv2d_bf16_infer_packed_elems(int Cin, int Cout);
+int sassd_conv2d_bf16_infer_pack_weight(const float *w, int Cout, int Cin, void *packed, void *stream);
+int sassd_conv2d_bf16_infer_fwd(const void *x, const void *w_packed, const float *scale, const float *shift, int relu, void *y,
+                                int y_bf16, int batch, int Cin, int Cout, int H, int W, void *stream);
+/* 1x1 (BEV conv7: BatchNorm + ReLU, bf16 out; the fused SSD head: bias, fp32 out; the part-sensitive 28 -> 28 conv: fp32 out)
+ * on the kernel of sassd_conv1x1_bf16_fwd, weights from sassd_conv1x1_bf16_pack_weight.  Supported shapes are those of
+ * sassd_conv1x1_bf16_supported.  x 4-byte, the pack 16-byte, y 8-byte (bf16) / 16-byte (fp32) aligned. */
+int sassd_conv1x1_bf16_infer_supported(int Cin, int Cout, int HW);
+int sassd_conv1x1_bf16_infer_fwd(const void *x, const void *w_packed, const float *scale, const float *shift, int relu, void *y,
+                                 int y_bf16, int batch, int Cin, int Cout, int HW, void *stream);
 
 /* Training: weight gradient of the same convolutions (autograd of nn.Conv2d at cmn.py:240-262 and
  * ssd_rotate_head.py:120-125,424-429; cuDNN in the reference).  x [B,Cin,H,W], dy [B,Cout,H,W] NCHW fp32 ->

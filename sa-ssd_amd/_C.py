@@ -61,6 +61,8 @@ _SIGS = {
     "sassd_spconv_bwd_weight_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "sassd_spconv_bwd_weight": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _SZ, _P]),
     "sassd_densify": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "sassd_densify_bf16_supported": (_I, [_I, _I, _I, _I]),
+    "sassd_densify_bf16": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "sassd_conv2d_packed_floats": (_SZ, [_I, _I, _I]),
     "sassd_conv2d_pack_weight": (_I, [_P, _I, _I, _I, _P, _P]),
     "sassd_conv2d_fwd": (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
@@ -110,6 +112,12 @@ _SIGS = {
     "sassd_conv1x1_bf16_packed_elems": (_SZ, [_I, _I]),
     "sassd_conv1x1_bf16_pack_weight": (_I, [_P, _I, _I, _I, _P, _P]),
     "sassd_conv1x1_bf16_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "sassd_conv2d_bf16_infer_supported": (_I, [_I, _I, _I, _I]),
+    "sassd_conv2d_bf16_infer_packed_elems": (_SZ, [_I, _I]),
+    "sassd_conv2d_bf16_infer_pack_weight": (_I, [_P, _I, _I, _P, _P]),
+    "sassd_conv2d_bf16_infer_fwd": (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "sassd_conv1x1_bf16_infer_supported": (_I, [_I, _I, _I]),
+    "sassd_conv1x1_bf16_infer_fwd": (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "sassd_conv2d_wgrad_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I]),
     "sassd_conv2d_bwd_weight": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "sassd_assign_targets_workspace_bytes": (_SZ, [_I, _I, _I]),

@@ -17,6 +17,8 @@
 // one 8-byte LDS write into a wave-private [64 co][64 px] image and the image leaves as 16-byte row stores.  No barriers: the
 // four waves of a workgroup (the four 64-channel groups of a 256-channel layer) read the same x tile at about the same time,
 // i.e. from L1 / L2; HBM sees every map once.
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -26,6 +28,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kPix = 64;            // pixels per tile
 constexpr int kImgPitch = 68;       // floats per row of the epilogue image (16 x 17 bytes: conflict-free 16-byte reads)
@@ -39,6 +42,11 @@ struct C1Params {
     int ng;                 // 64-channel output groups
     int ntile;              // tiles per image
     int T;                  // B * ntile
+    // INF = 1 (bf16 inference): x is a bf16 map (`xh`); epilogue relu?(acc * scale + shift) (acc + shift without a scale),
+    // stored as bf16 or fp32
+    const unsigned short *xh;
+    const float *scale;
+    int relu, y_bf16;
 };
 
 __device__ __forceinline__ unsigned pack_bf16(float a, float b)
@@ -64,9 +72,13 @@ __global__ void conv1x1_bf16_pack_kernel(const float *__restrict__ w, int Cout, 
     out[i] = __builtin_bit_cast(unsigned short, (__bf16)v);
 }
 
-template <int KS>
+// INF = 1: a lane's pixel pair of one channel is a single 4-byte load of two bf16 (the fp32 form loads 8 bytes and rounds);
+// the even and odd halves are regrouped into the two B fragments.  INF = 0 is the training kernel, unchanged.
+template <int KS, int INF = 0>
 __global__ void __launch_bounds__(256) conv1x1_bf16_kernel(C1Params P)
 {
+    using XT = std::conditional_t<INF != 0, unsigned short, float>;
+    using RT = std::conditional_t<INF != 0, unsigned, f32x2>;          // one channel of a lane's pixel pair
     constexpr int GS = KS < 2 ? KS : 2;             // k-steps per load group
     constexpr int NG = KS / GS;                     // groups per tile
     static_assert(KS % GS == 0, "whole groups");
@@ -92,25 +104,26 @@ __global__ void __launch_bounds__(256) conv1x1_bf16_kernel(C1Params P)
         ci = ci < P.Cin ? ci : P.Cin - 1;
         last_off[i] = (unsigned)(ci - 16 * KSF) * HW;
     }
-    struct Tile { const float *base; unsigned pix; };
+    struct Tile { const XT *base; unsigned pix; };
     auto tile_of = [&](int t) -> Tile {
         const int b = t / P.ntile, pt = t - b * P.ntile;
         const int room = P.HW - 2 - pt * kPix;                          // last pixel pair inside the map, tile-relative
         Tile r;
-        r.base = P.x + (size_t)b * P.Cin * HW + (size_t)pt * kPix;
+        if constexpr (INF) r.base = P.xh + (size_t)b * P.Cin * HW + (size_t)pt * kPix;
+        else r.base = P.x + (size_t)b * P.Cin * HW + (size_t)pt * kPix;
         r.pix = (unsigned)min(2 * n, room);
         return r;
     };
-    f32x2 raw[2][GS][8];
-    auto issue = [&](const Tile &tl, int grp, f32x2 (&dst)[GS][8]) {
+    RT raw[2][GS][8];
+    auto issue = [&](const Tile &tl, int grp, RT (&dst)[GS][8]) {
 #pragma unroll
         for (int q = 0; q < GS; ++q) {
             const int ks = grp * GS + q;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const float *sb = tl.base + (size_t)(16 * ks + (ks < KSF ? i : 0)) * HW;           // wave-uniform
-                const unsigned vo = (ks < KSF ? chan_off : last_off[i]) + tl.pix;                   // per lane, floats
-                dst[q][i] = *reinterpret_cast<const f32x2 *>(reinterpret_cast<const char *>(sb) + (size_t)vo * 4u);
+                const XT *sb = tl.base + (size_t)(16 * ks + (ks < KSF ? i : 0)) * HW;              // wave-uniform
+                const unsigned vo = (ks < KSF ? chan_off : last_off[i]) + tl.pix;                   // per lane, elements
+                dst[q][i] = *reinterpret_cast<const RT *>(reinterpret_cast<const char *>(sb) + (size_t)vo * sizeof(XT));
             }
         }
     };
@@ -144,12 +157,17 @@ __global__ void __launch_bounds__(256) conv1x1_bf16_kernel(C1Params P)
             else if (NG > 1 && tn < P.T) issue(xn, 0, raw[0]);
 #pragma unroll
             for (int q = 0; q < GS; ++q) {
-                const f32x2(&v)[8] = raw[grp & 1][q];
+                const RT(&v)[8] = raw[grp & 1][q];
                 u32x4 be, bo;
 #pragma unroll
                 for (int h = 0; h < 4; ++h) {
-                    be[h] = pack_bf16(v[2 * h][0], v[2 * h + 1][0]);
-                    bo[h] = pack_bf16(v[2 * h][1], v[2 * h + 1][1]);
+                    if constexpr (INF) {        // v[c] = (even pixel | odd pixel << 16) of channel c
+                        be[h] = (v[2 * h] & 0xffffu) | (v[2 * h + 1] << 16);
+                        bo[h] = (v[2 * h] >> 16) | (v[2 * h + 1] & 0xffff0000u);
+                    } else {
+                        be[h] = pack_bf16(v[2 * h][0], v[2 * h + 1][0]);
+                        bo[h] = pack_bf16(v[2 * h][1], v[2 * h + 1][1]);
+                    }
                 }
                 const int ks = grp * GS + q;
 #pragma unroll
@@ -174,6 +192,31 @@ __global__ void __launch_bounds__(256) conv1x1_bf16_kernel(C1Params P)
         for (int i = 0; i < 16; ++i) {
             const int row = 4 * i + (lane >> 4);
             f32x4 v = *reinterpret_cast<const f32x4 *>(img + row * kImgPitch + 4 * c4);
+            if constexpr (INF) {
+                const int co = 64 * g + row;
+                if (co < P.Cout && p < P.HW) {
+                    const float sh = P.shift ? P.shift[co] : 0.f;
+                    if (P.scale) {
+                        const float sc = P.scale[co];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) v[k] = fmaf(v[k], sc, sh);
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) v[k] += sh;
+                    }
+                    if (P.relu) {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) v[k] = v[k] > 0.f ? v[k] : 0.f;
+                    }
+                    const size_t off = ((size_t)b * P.Cout + co) * HW + p;
+                    if (P.y_bf16)
+                        *reinterpret_cast<u32x2 *>(reinterpret_cast<unsigned short *>(P.y) + off) =
+                            (u32x2){pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3])};
+                    else
+                        *reinterpret_cast<f32x4 *>(P.y + off) = v;
+                }
+                continue;
+            }
             if (64 * g + row < P.Cout && p < P.HW) {                      // (HW % 4 == 0: a quad is inside or outside)
                 if (P.shift) {
                     const float sh = P.shift[64 * g + row];
@@ -211,20 +254,16 @@ extern "C" int sassd_conv1x1_bf16_pack_weight(const float *w, int Cout, int Cin,
     return sassd_launch_status();
 }
 
-extern "C" int sassd_conv1x1_bf16_fwd(const float *x, const void *w_packed, const float *shift, float *y, int batch, int Cin,
-                                      int Cout, int HW, void *stream_)
+namespace {
+// grid + dispatch shared by the training (INF = 0) and the inference (INF = 1) forms; P has its pointers and shape set
+template <int INF>
+int c1_launch(C1Params &P, hipStream_t stream)
 {
-    if (!x || !w_packed || !y || batch < 1 || !sassd_conv1x1_bf16_supported(Cin, Cout, HW)) return SASSD_EINVAL;
-    if (((uintptr_t)x & 7) || ((uintptr_t)y & 15) || ((uintptr_t)w_packed & 15)) return SASSD_EINVAL;
-    hipStream_t stream = (hipStream_t)stream_;
-    C1Params P;
-    P.x = x; P.wp = (const u32x4 *)w_packed; P.shift = shift; P.y = y;
-    P.B = batch; P.Cin = Cin; P.Cout = Cout; P.HW = HW;
-    P.ng = cdiv(Cout, 64);
-    P.ntile = cdiv(HW, kPix);
-    if ((long)batch * P.ntile > 0x7fffffffL) return SASSD_EINVAL;
-    P.T = batch * P.ntile;
-    const int KS = c1_ksteps(Cin);
+    P.ng = cdiv(P.Cout, 64);
+    P.ntile = cdiv(P.HW, kPix);
+    if ((long)P.B * P.ntile > 0x7fffffffL) return SASSD_EINVAL;
+    P.T = P.B * P.ntile;
+    const int KS = c1_ksteps(P.Cin);
     // Workgroups: one per CU for the register-heavy forms (KS >= 8: 128 weight registers), two otherwise (the 70 KB epilogue
     // image); the tile streams -- 4 / ng per workgroup -- get equal runs of tiles.
     int ncu = 256;
@@ -247,10 +286,10 @@ extern "C" int sassd_conv1x1_bf16_fwd(const float *x, const void *w_packed, cons
     int slot = 0;
 #define SASSD_C1_GO(KSV, SLOT)                                                                                             \
     {                                                                                                                      \
-        fn = (const void *)conv1x1_bf16_kernel<KSV>; slot = SLOT;                                                          \
+        fn = (const void *)conv1x1_bf16_kernel<KSV, INF>; slot = SLOT;                                                     \
         int rc = sassd_dyn_lds(fn, lds, done[slot]);                                                                       \
         if (rc) return rc;                                                                                                 \
-        hipLaunchKernelGGL(conv1x1_bf16_kernel<KSV>, dim3(grid), dim3(256), lds, stream, P);                               \
+        hipLaunchKernelGGL((conv1x1_bf16_kernel<KSV, INF>), dim3(grid), dim3(256), lds, stream, P);                        \
     }
     switch (KS) {
     case 1: SASSD_C1_GO(1, 0) break;
@@ -262,4 +301,33 @@ extern "C" int sassd_conv1x1_bf16_fwd(const float *x, const void *w_packed, cons
 #undef SASSD_C1_GO
     (void)fn; (void)slot;
     return sassd_launch_status();
+}
+}  // namespace
+
+extern "C" int sassd_conv1x1_bf16_fwd(const float *x, const void *w_packed, const float *shift, float *y, int batch, int Cin,
+                                      int Cout, int HW, void *stream_)
+{
+    if (!x || !w_packed || !y || batch < 1 || !sassd_conv1x1_bf16_supported(Cin, Cout, HW)) return SASSD_EINVAL;
+    if (((uintptr_t)x & 7) || ((uintptr_t)y & 15) || ((uintptr_t)w_packed & 15)) return SASSD_EINVAL;
+    C1Params P;
+    P.x = x; P.wp = (const u32x4 *)w_packed; P.shift = shift; P.y = y;
+    P.xh = nullptr; P.scale = nullptr; P.relu = 0; P.y_bf16 = 0;
+    P.B = batch; P.Cin = Cin; P.Cout = Cout; P.HW = HW;
+    return c1_launch<0>(P, (hipStream_t)stream_);
+}
+
+// ---- bf16 inference (InferencePlan(precision="bf16")): BEVNet conv7 (eval BatchNorm + ReLU, bf16 out), the fused SSD head
+// (bias, fp32 out) and the part-sensitive 1x1 (fp32 out) on a bf16 map; weights from sassd_conv1x1_bf16_pack_weight.
+extern "C" int sassd_conv1x1_bf16_infer_supported(int Cin, int Cout, int HW) { return sassd_conv1x1_bf16_supported(Cin, Cout, HW); }
+
+extern "C" int sassd_conv1x1_bf16_infer_fwd(const void *x, const void *w_packed, const float *scale, const float *shift, int relu,
+                                            void *y, int y_bf16, int batch, int Cin, int Cout, int HW, void *stream_)
+{
+    if (!x || !w_packed || !y || batch < 1 || !sassd_conv1x1_bf16_infer_supported(Cin, Cout, HW)) return SASSD_EINVAL;
+    if (((uintptr_t)x & 3) || ((uintptr_t)y & (y_bf16 ? 7 : 15)) || ((uintptr_t)w_packed & 15)) return SASSD_EINVAL;
+    C1Params P;
+    P.x = nullptr; P.xh = (const unsigned short *)x; P.wp = (const u32x4 *)w_packed; P.scale = scale; P.shift = shift;
+    P.relu = relu ? 1 : 0; P.y = (float *)y; P.y_bf16 = y_bf16 ? 1 : 0;
+    P.B = batch; P.Cin = Cin; P.Cout = Cout; P.HW = HW;
+    return c1_launch<1>(P, (hipStream_t)stream_);
 }

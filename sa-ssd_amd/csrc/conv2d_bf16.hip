@@ -31,6 +31,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kTR = 10, kTC = 16;              // largest output tile: rows x columns
 constexpr int kNPB = kTR / 2;                  // ... = 5 MFMA pixel blocks of 2 rows x 16 columns
@@ -60,6 +61,11 @@ struct BfParams {
     int mma_prio;                                  // 1: MMA waves at s_setprio 1 (default); 0: none; 2: loader waves at 2
     const float *in_aff;                           // BN = 1: [3][Cin] mean | invstd * gamma | beta of the BatchNorm + ReLU the
                                                    // loader waves apply to the input on its way into LDS (round 6)
+    // INF = 1 (bf16 inference): x is a bf16 map (`xh`), the epilogue is relu?(acc * scale + shift) (or acc + shift without a
+    // scale) stored as bf16 or fp32; y holds Cy <= Cout maps (the couts past Cy are padding: computed, never stored)
+    const unsigned short *xh;
+    const float *scale;
+    int relu, y_bf16, Cy;
 };
 
 __device__ __forceinline__ unsigned pack2(float lo, float hi)
@@ -68,8 +74,9 @@ __device__ __forceinline__ unsigned pack2(float lo, float hi)
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
 }
 
-// w fp32 [Cout][Cin][3][3] -> bf16 [tap][CinP/8][Cout][8], CinP = Cin rounded up to 32 (zero weights for the padding)
-__global__ void bf16_pack_kernel(const float *__restrict__ w, int Cout, int Cin, int CinP,
+// w fp32 [CoutW][Cin][3][3] -> bf16 [tap][CinP/8][Cout][8], CinP = Cin rounded up to 32, Cout >= CoutW (zero weights for the
+// padding of either)
+__global__ void bf16_pack_kernel(const float *__restrict__ w, int Cout, int CoutW, int Cin, int CinP,
                                  unsigned short *__restrict__ out)
 {
     const size_t n = (size_t)9 * CinP * Cout;
@@ -81,7 +88,7 @@ __global__ void bf16_pack_kernel(const float *__restrict__ w, int Cout, int Cin,
     const int c8 = r % (CinP / 8);
     const int tap = r / (CinP / 8);
     const int ci = c8 * 8 + j;
-    const float v = ci < Cin ? w[((size_t)co * Cin + ci) * 9 + tap] : 0.f;
+    const float v = ci < Cin && co < CoutW ? w[((size_t)co * Cin + ci) * 9 + tap] : 0.f;
     out[i] = __builtin_bit_cast(unsigned short, (__bf16)v);
 }
 
@@ -100,8 +107,9 @@ __global__ void bf16_pack_kernel(const float *__restrict__ w, int Cout, int Cin,
 // image area for that reason), and the weight ring keeps running from one tile into the next.
 // A variant with 64 couts per MMA wave (4 MMA + 4 loader waves, every B fragment feeding two MFMAs) was built and measured
 // in round 3: 0.104 ms against 0.104 ms -- neither LDS reads nor MFMA-pipe sharing bound the kernel.
+template <typename XT>
 struct LoadTile {                                  // what the loader waves need of a tile
-    const float *xb;                               // image base
+    const XT *xb;                                  // image base
     int r0, c0, rows;                              // first output row / column, live LDS rows (2 nb + 2)
 };
 
@@ -110,9 +118,16 @@ struct LoadTile {                                  // what the loader waves need
 // max(z, 0): the very expression of bn2d_apply_kernel, so the operand that reaches the MFMA is bit-identical to the one the
 // stand-alone apply pass would have written -- before they round it to bf16.  The normalised map is never written to HBM
 // (72 MB written + read back per 256-channel layer at batch 2 = the 20.7 us bn2d_apply_kernel took).
-template <int COW, int NLW, int DBG, int BN = 0>
+// INF = 1 (bf16 inference): the input map is already bf16, so a loader item loads 8 bytes (4 pixels) per channel plane and
+// its LDS stores are the loaded bits, re-interleaved; the epilogue is the eval BatchNorm + ReLU in fp32 on the accumulator and
+// rounds at the store when the consumer is another convolution.  INF = 0 is the training kernel, unchanged.
+template <int COW, int NLW, int DBG, int BN = 0, int INF = 0>
 __global__ void __launch_bounds__(64 * (COW + NLW), 3) conv2d_bf16_kernel(BfParams p)
 {
+    static_assert(!(BN && INF), "the inference form reads normalised bf16 maps");
+    using XT = std::conditional_t<INF != 0, unsigned short, float>;
+    using ST = std::conditional_t<INF != 0, u32x2, f32x4>;             // one plane load: 4 pixels
+    using LT = LoadTile<XT>;
     constexpr int NLT = 64 * NLW;                  // loader threads
     constexpr int RING = 6;                        // weight fragment steps in flight per MMA wave (18 % RING == 0)
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];     // 2 input buffers | COW images | tile list
@@ -174,12 +189,13 @@ __global__ void __launch_bounds__(64 * (COW + NLW), 3) conv2d_bf16_kernel(BfPara
         auto tile_geom = [&](int t) {
             const int strip = tl[1 + 3 * t], blk = tl[2 + 3 * t], nb = tl[3 + 3 * t];
             const int tx = strip % p.tiles_x, b = (strip / p.tiles_x) % p.B;
-            LoadTile T;
-            T.xb = p.x + (size_t)b * p.Cin * hw;
+            LT T;
+            if constexpr (INF) T.xb = p.xh + (size_t)b * p.Cin * hw;
+            else T.xb = p.x + (size_t)b * p.Cin * hw;
             T.r0 = 2 * blk; T.c0 = tx * kTC; T.rows = 2 * nb + 2;
             return T;
         };
-        auto item_geom = [&](int e, const LoadTile &T, bool &live, bool &ok, int &dst_off, const float *&q, int &g) {
+        auto item_geom = [&](int e, const LT &T, bool &live, bool &ok, int &dst_off, const XT *&q, int &g) {
             // channel group fastest: the 8 lanes of one ds_write_b128 phase hold 4 groups x 2 pixel quads = 8 different
             // 16-byte slots of the 128-byte bank window (slot = (4 (qd & 1) + 5 px + g) mod 8 with the 80-byte pixel pitch).
             // With the quad fastest (round 2) they fell on 2 slots: 4-way conflicts, 32 LDS cycles per store instead of 8.
@@ -192,22 +208,39 @@ __global__ void __launch_bounds__(64 * (COW + NLW), 3) conv2d_bf16_kernel(BfPara
             q = T.xb + (ok ? (size_t)yy * p.W + xx : 0);
             dst_off = row * kRowB + 4 * qd * kPixB + g * 16;
         };
-        auto item_issue = [&](int e, const LoadTile &T, f32x4 (&st)[8], int ci0) {
-            bool live, ok; int d, g; const float *q;
+        auto item_issue = [&](int e, const LT &T, ST (&st)[8], int ci0) {
+            bool live, ok; int d, g; const XT *q;
             item_geom(e, T, live, ok, d, q, g);
             if (!live) return;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int ch = ok ? min(ci0 + g * 8 + j, p.Cin - 1) : 0;
-                const float *a = q + (size_t)ch * hw;
-                asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(st[j]) : "v"(a));
+                const XT *a = q + (size_t)ch * hw;
+                if constexpr (INF) asm volatile("global_load_dwordx2 %0, %1, off" : "=&v"(st[j]) : "v"(a));
+                else asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(st[j]) : "v"(a));
             }
         };
-        auto item_store = [&](int e, const LoadTile &T, const f32x4 (&st)[8], int buf, int ci0) {
-            bool live, ok; int d, g; const float *q;
+        auto item_store = [&](int e, const LT &T, const ST (&st)[8], int buf, int ci0) {
+            bool live, ok; int d, g; const XT *q;
             item_geom(e, T, live, ok, d, q, g);
             if (!live) return;
             unsigned char *dst = lds + buf * kBufB + d;
+            if constexpr (INF) {
+                // st[j] = channel plane j, pixels 0..3 as bf16 pairs (pixel 2h in the low half of word h) -> per pixel, the
+                // channel pairs (2j, 2j + 1) of one 16-byte channel vector
+#pragma unroll
+                for (int px = 0; px < 4; ++px) {
+                    u32x4 v4;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const unsigned lo = st[2 * j][px >> 1], hi = st[2 * j + 1][px >> 1];
+                        const unsigned v = (px & 1) ? (lo >> 16) | (hi & 0xffff0000u) : (lo & 0xffffu) | (hi << 16);
+                        v4[j] = ok ? v : 0u;
+                    }
+                    *(u32x4 *)(dst + px * kPixB) = v4;
+                }
+                return;
+            }
             float am[8], as[8], ab[8];
             if constexpr (BN) {
                 const float *a0 = aff + ci0 + g * 8;
@@ -237,14 +270,18 @@ __global__ void __launch_bounds__(64 * (COW + NLW), 3) conv2d_bf16_kernel(BfPara
         };
         static_assert(kItems <= 2 * NLT, "a loader thread owns at most two items");
         const bool one = lt < kItems, two = lt + NLT < kItems;
-        f32x4 s0[8], s1[8];
+        ST s0[8], s1[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { s0[j] = (f32x4){0.f, 0.f, 0.f, 0.f}; s1[j] = s0[j]; }
-        auto issue = [&](const LoadTile &T, int ci0) {
+        for (int j = 0; j < 8; ++j) {
+            if constexpr (INF) s0[j] = (u32x2){0u, 0u};
+            else s0[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            s1[j] = s0[j];
+        }
+        auto issue = [&](const LT &T, int ci0) {
             if (one) item_issue(lt, T, s0, ci0);
             if (two) item_issue(lt + NLT, T, s1, ci0);
         };
-        auto land = [&](const LoadTile &T, int buf, int ci0) {   // every hand-issued load of this wave has returned; registers -> LDS
+        auto land = [&](const LT &T, int buf, int ci0) {   // every hand-issued load of this wave has returned; registers -> LDS
             asm volatile("s_waitcnt vmcnt(0)"
                          : "+v"(s0[0]), "+v"(s0[1]), "+v"(s0[2]), "+v"(s0[3]), "+v"(s0[4]), "+v"(s0[5]), "+v"(s0[6]), "+v"(s0[7]),
                            "+v"(s1[0]), "+v"(s1[1]), "+v"(s1[2]), "+v"(s1[3]), "+v"(s1[4]), "+v"(s1[5]), "+v"(s1[6]), "+v"(s1[7]));
@@ -253,8 +290,8 @@ __global__ void __launch_bounds__(64 * (COW + NLW), 3) conv2d_bf16_kernel(BfPara
         };
         // two cursors over the (tile, chunk) sequence: the one being landed and the one being issued (one step ahead of it)
         int t_land = 0, c_land = 0, t_iss = 0, c_iss = 0;
-        LoadTile Tl = tile_geom(0), Ti = Tl;
-        auto advance = [&](int &t, int &c, LoadTile &T) {
+        LT Tl = tile_geom(0), Ti = Tl;
+        auto advance = [&](int &t, int &c, LT &T) {
             if (++c == nchunk) { c = 0; ++t; if (t < ntile) T = tile_geom(t); }
         };
         issue(Ti, 0);
@@ -434,6 +471,30 @@ __global__ void __launch_bounds__(64 * (COW + NLW), 3) conv2d_bf16_kernel(BfPara
                     const f32x4 v4 = *(const f32x4 *)(img + col * kEP + px);
                     const int co = co_w + col;
                     const int yy = r0 + 2 * n + (px >> 4), xx = c0 + (px & 15);
+                    if constexpr (INF) {
+                        if (yy < p.H && xx < p.W && co < p.Cy) {
+                            const float sh = p.shift ? p.shift[co] : 0.f;
+                            f32x4 o = v4;
+                            if (p.scale) {
+                                const float sc = p.scale[co];
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) o[k] = fmaf(o[k], sc, sh);
+                            } else {
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) o[k] += sh;
+                            }
+                            if (p.relu) {
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) o[k] = o[k] > 0.f ? o[k] : 0.f;
+                            }
+                            const size_t off = ((size_t)b * p.Cy + co) * hw + (size_t)yy * p.W + xx;
+                            if (p.y_bf16)
+                                *(u32x2 *)((unsigned short *)p.y + off) = (u32x2){pack2(o[0], o[1]), pack2(o[2], o[3])};
+                            else
+                                *(f32x4 *)(p.y + off) = o;
+                        }
+                        continue;
+                    }
                     if (yy < p.H && xx < p.W) {                     // W % 4 == 0: a quad is inside or outside as a whole
                         const float sh = p.shift ? p.shift[co] : 0.f;
                         *(f32x4 *)(yb + (size_t)co * hw + (size_t)yy * p.W + xx) =
@@ -477,21 +538,21 @@ extern "C" int sassd_conv2d_bf16_pack_weight(const float *w, int Cout, int Cin, 
     if (!w || !packed || Cin < 1 || Cout < 1) return SASSD_EINVAL;
     const size_t n = sassd_conv2d_bf16_packed_elems(Cin, Cout);
     hipLaunchKernelGGL(bf16_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, w, Cout,
-                       Cin, (int)align_up(Cin, 32), (unsigned short *)packed);
+                       Cout, Cin, (int)align_up(Cin, 32), (unsigned short *)packed);
     return sassd_launch_status();
 }
 
 namespace {
-template <int COW, int DBG, int BN = 0>
+template <int COW, int DBG, int BN = 0, int INF = 0>
 int launch_bf16(const BfParams &p, int nwg, hipStream_t s)
 {
     static std::atomic<unsigned long long> attr_done{0};
     const size_t tl_b = (size_t)4 * ((1 + 3 * kMaxTiles + 3) / 4) * sizeof(int);
     const size_t lds_max = align_up((size_t)2 * kBufB + (size_t)COW * kImgB + tl_b + (BN ? (size_t)3 * 1024 * 4 : 0), 16);
     const size_t lds = align_up((size_t)2 * kBufB + (size_t)COW * kImgB + tl_b + (BN ? (size_t)3 * p.CinP * 4 : 0), 16);
-    const int rc = sassd_dyn_lds((const void *)conv2d_bf16_kernel<COW, 4, DBG, BN>, lds_max, attr_done);
+    const int rc = sassd_dyn_lds((const void *)conv2d_bf16_kernel<COW, 4, DBG, BN, INF>, lds_max, attr_done);
     if (rc != SASSD_OK) return rc;
-    hipLaunchKernelGGL((conv2d_bf16_kernel<COW, 4, DBG, BN>), dim3((unsigned)nwg), dim3(64 * (COW + 4)), lds, s, p);
+    hipLaunchKernelGGL((conv2d_bf16_kernel<COW, 4, DBG, BN, INF>), dim3((unsigned)nwg), dim3(64 * (COW + 4)), lds, s, p);
     return sassd_launch_status();
 }
 }  // namespace
@@ -504,6 +565,7 @@ static int conv2d_bf16_launch(const float *x, const float *in_aff, const void *w
     if (in_aff && Cin > 1024) return SASSD_EINVAL;
     BfParams p;
     p.x = x; p.wp = (const unsigned short *)w_packed; p.shift = shift; p.y = y; p.in_aff = in_aff;
+    p.xh = nullptr; p.scale = nullptr; p.relu = 0; p.y_bf16 = 0; p.Cy = Cout;
     p.B = batch; p.Cin = Cin; p.CinP = (int)align_up(Cin, 32); p.Cout = Cout; p.H = H; p.W = W;
     p.tiles_x = cdiv(W, kTC); p.hb = cdiv(H, 2);
     // 256-cout workgroups (8 MMA waves) when they divide Cout; 160-cout ones (5 MMA waves) when THEY do -- Cout = 320, the data
@@ -563,4 +625,59 @@ extern "C" int sassd_conv2d_bf16_bnrelu_fwd(const float *x, const float *in_affi
 {
     if (!in_affine) return SASSD_EINVAL;
     return conv2d_bf16_launch(x, in_affine, w_packed, shift, y, batch, Cin, Cout, H, W, 0, stream_);
+}
+
+// ---- bf16 inference (InferencePlan(precision="bf16")): bf16 NCHW map in, eval BatchNorm + ReLU (or a bias) on the fp32
+// accumulator, bf16 (next convolution) or fp32 map out.  The weights are the raw conv weights, packed once at Cout rounded up
+// to 32 (zero rows for the padding): the 28-map part-sensitive conv runs as a 32-cout tile and stores its first 28 maps.
+extern "C" int sassd_conv2d_bf16_infer_supported(int Cin, int Cout, int H, int W)
+{
+    return Cin >= 1 && Cout >= 1 && H >= 1 && W >= 16 && W % 4 == 0;
+}
+
+extern "C" size_t sassd_conv2d_bf16_infer_packed_elems(int Cin, int Cout)
+{
+    if (Cin < 1 || Cout < 1) return 0;
+    return sassd_conv2d_bf16_packed_elems(Cin, (int)align_up(Cout, 32));
+}
+
+extern "C" int sassd_conv2d_bf16_infer_pack_weight(const float *w, int Cout, int Cin, void *packed, void *stream_)
+{
+    if (!w || !packed || Cin < 1 || Cout < 1) return SASSD_EINVAL;
+    const int CoutP = (int)align_up(Cout, 32);
+    const size_t n = sassd_conv2d_bf16_packed_elems(Cin, CoutP);
+    hipLaunchKernelGGL(bf16_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, w, CoutP,
+                       Cout, Cin, (int)align_up(Cin, 32), (unsigned short *)packed);
+    return sassd_launch_status();
+}
+
+extern "C" int sassd_conv2d_bf16_infer_fwd(const void *x, const void *w_packed, const float *scale, const float *shift, int relu,
+                                           void *y, int y_bf16, int batch, int Cin, int Cout, int H, int W, void *stream_)
+{
+    if (!x || !w_packed || !y || batch < 1 || !sassd_conv2d_bf16_infer_supported(Cin, Cout, H, W)) return SASSD_EINVAL;
+    if (((uintptr_t)x & 7) || ((uintptr_t)w_packed & 15) || ((uintptr_t)y & (y_bf16 ? 7 : 15))) return SASSD_EINVAL;
+    const int CoutP = (int)align_up(Cout, 32);
+    // 256-cout workgroups (8 MMA waves) when they divide the padded Cout, one MMA wave for a single 32-cout tile (the
+    // part-sensitive conv: no idle MMA waves next to the four loader waves), else 128-cout workgroups
+    const int cot = CoutP % 256 == 0 ? 256 : CoutP == 32 ? 32 : 128;
+    BfParams p;
+    p.x = nullptr; p.xh = (const unsigned short *)x; p.wp = (const unsigned short *)w_packed; p.in_aff = nullptr;
+    p.scale = scale; p.shift = shift; p.relu = relu ? 1 : 0; p.y = (float *)y; p.y_bf16 = y_bf16 ? 1 : 0; p.Cy = Cout;
+    p.B = batch; p.Cin = Cin; p.CinP = (int)align_up(Cin, 32); p.Cout = CoutP; p.H = H; p.W = W;
+    p.tiles_x = cdiv(W, kTC); p.hb = cdiv(H, 2);
+    const long strips = (long)cdiv(CoutP, cot) * batch * p.tiles_x;
+    if (strips > 0x7fffffffL / p.hb) return SASSD_EINVAL;
+    const long G = strips * p.hb;
+    p.strips = (int)strips;
+    p.wr_map = 1; p.mma_prio = 1;
+    int cus = 0;
+    const int rc = sassd_num_cus(&cus);
+    if (rc != SASSD_OK) return rc;
+    cus = (int)align_up((size_t)cus, 8);
+    long nwg = (long)cus * ((G + (long)cus * 40 - 1) / ((long)cus * 40));          // (the training launcher's geometry)
+    if (G < 4 * nwg) nwg = (long)align_up((size_t)((G + 3) / 4), 8);
+    hipStream_t s = (hipStream_t)stream_;
+    if (cot == 256) return launch_bf16<8, 0, 0, 1>(p, (int)nwg, s);
+    if (cot == 32) return launch_bf16<1, 0, 0, 1>(p, (int)nwg, s);
+    return launch_bf16<4, 0, 0, 1>(p, (int)nwg, s);
 }

@@ -590,6 +590,20 @@ __global__ void densify_kernel(const float *__restrict__ feats, const int32_t *_
     out[(((size_t)p.x * C * D + ch) * H + p.z) * W + p.w] = feats[(size_t)row * C + c];
 }
 
+// bf16 inference (InferencePlan(precision="bf16")): the same scatter, each feature rounded to bf16 (nearest even) -- the operand
+// BEV conv0 would round at its load
+__global__ void densify_bf16_kernel(const float *__restrict__ feats, const int32_t *__restrict__ idx,
+                                    const int32_t *__restrict__ n_ptr, int cap, int C, int D, int H, int W, int order,
+                                    unsigned short *__restrict__ out)
+{
+    const int n = min(*n_ptr, cap);
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * C) return;
+    const int c = t / n, row = t - c * n;
+    const int4 p = ((const int4 *)idx)[row];
+    const int ch = order ? (p.y * C + c) : (c * D + p.y);
+    out[(((size_t)p.x * C * D + ch) * H + p.z) * W + p.w] = __builtin_bit_cast(unsigned short, (__bf16)feats[(size_t)row * C + c]);
+}
 
 // ------------------------------------------------------------------------------------------------------------------
 // Backward (training; replaces spconv `indice_conv_backward_fp32`):
@@ -960,5 +974,28 @@ extern "C" int sassd_densify(const float *feats, const int32_t *indices, const i
     } else if ((rc = sassd_hip(hipMemsetAsync(out, 0, obytes, stream)))) return rc;
     hipLaunchKernelGGL(densify_kernel, dim3(cdiv(cap * C, 256)), dim3(256), 0, stream, feats, indices, n_ptr, cap, C, D,
                        H, W, channel_order, out);
+    return sassd_launch_status();
+}
+
+extern "C" int sassd_densify_bf16_supported(int C, int D, int H, int W)
+{
+    // (the map is cleared by the fill kernel, 16 bytes per store: every channel plane a whole number of 16-byte pieces)
+    return C >= 1 && D >= 1 && H >= 1 && W >= 1 && ((size_t)H * W) % 8 == 0;
+}
+
+extern "C" int sassd_densify_bf16(const float *feats, const int32_t *indices, const int32_t *n_ptr, int cap, int C, int D, int H,
+                                  int W, int batch_size, int channel_order, void *out, void *stream_)
+{
+    if (!feats || !indices || !n_ptr || !out || cap <= 0 || batch_size < 1 || !sassd_densify_bf16_supported(C, D, H, W))
+        return SASSD_EINVAL;
+    if ((uintptr_t)out & 15) return SASSD_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc;
+    // a fill kernel, never hipMemsetAsync (a memset node in a captured frame graph)
+    const size_t obytes = (size_t)batch_size * C * D * H * W * sizeof(unsigned short);
+    if ((rc = sassd_fill2(out, obytes, 0, out, 0, 0, stream))) return rc;
+    if ((rc = sassd_launch_status())) return rc;
+    hipLaunchKernelGGL(densify_bf16_kernel, dim3(cdiv(cap * C, 256)), dim3(256), 0, stream, feats, indices, n_ptr, cap, C, D,
+                       H, W, channel_order, (unsigned short *)out);
     return sassd_launch_status();
 }

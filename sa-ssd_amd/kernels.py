@@ -359,6 +359,23 @@ def densify(feats, indices, n_ptr, cap, shape, batch_size, channel_order=0, out=
     return out
 
 
+def densify_bf16_supported(c, shape):
+    d, h, w = shape
+    return bool(_C.lib().sassd_densify_bf16_supported(c, d, h, w))
+
+
+def densify_bf16(feats, indices, n_ptr, cap, shape, batch_size, channel_order=0, out=None):
+    """densify() into a bf16 map (every feature rounded to nearest even), cleared by a fill kernel."""
+    d, h, w = shape
+    c = feats.shape[1]
+    if out is None:
+        out = torch.empty(batch_size, c * d, h, w, dtype=torch.bfloat16, device=feats.device)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous()
+    _C.check(_C.lib().sassd_densify_bf16(_C.ptr(feats), _C.ptr(indices), _C.ptr(n_ptr), cap, c, d, h, w, batch_size,
+                                         channel_order, _C.ptr(out), _C.stream()), "sassd_densify_bf16")
+    return out
+
+
 # --------------------------------------------------------------------------------------------------
 def conv2d_pack_weight(w):
     """w [Cout, Cin, k, k] f32 cuda (torch layout) -> packed [Cin/8][k*k][8][CoutPad]."""
@@ -634,6 +651,59 @@ def conv1x1_bf16_fwd(x, w_packed, cout, shift=None, y=None):
         y = torch.empty(b, cout, h, w, dtype=torch.float32, device=x.device)
     _C.check(_C.lib().sassd_conv1x1_bf16_fwd(_C.ptr(x), _C.ptr(w_packed), _C.ptr(shift) if shift is not None else None,
                                              _C.ptr(y), b, cin, cout, h * w, _C.stream()), "sassd_conv1x1_bf16_fwd")
+    return y
+
+
+# ---- bf16 inference (InferencePlan(precision="bf16")): bf16 maps in, eval BatchNorm + ReLU / bias in fp32, bf16 or fp32 out
+def conv2d_bf16_infer_supported(cin, cout, h, w):
+    return bool(_C.lib().sassd_conv2d_bf16_infer_supported(cin, cout, h, w))
+
+
+def conv2d_bf16_infer_pack_weight(w):
+    """w [Cout,Cin,3,3] fp32 (raw weights, no BatchNorm folded in) -> bf16 pack at Cout rounded up to 32 (zero rows)."""
+    _chk_cuda(w)
+    cout, cin, kh, kw = w.shape
+    assert kh == 3 and kw == 3
+    L = _C.lib()
+    packed = torch.empty(L.sassd_conv2d_bf16_infer_packed_elems(cin, cout), dtype=torch.int16, device=w.device)
+    _C.check(L.sassd_conv2d_bf16_infer_pack_weight(_C.ptr(w.contiguous()), cout, cin, _C.ptr(packed), _C.stream()),
+             "sassd_conv2d_bf16_infer_pack_weight")
+    return packed
+
+
+def _infer_out(x, cout, y, out_bf16):
+    b, _, h, w = x.shape
+    if y is None:
+        y = torch.empty(b, cout, h, w, dtype=torch.bfloat16 if out_bf16 else torch.float32, device=x.device)
+    assert y.dtype == (torch.bfloat16 if out_bf16 else torch.float32) and y.is_contiguous() and y.shape == (b, cout, h, w)
+    return y
+
+
+def conv2d_bf16_infer_fwd(x, w_packed, cout, scale, shift, relu, y=None, out_bf16=True):
+    """3x3 pad-1 conv of a bf16 NCHW map: relu?(acc * scale + shift) (scale None: acc + shift), stored bf16 or fp32."""
+    _chk_cuda(x, w_packed)
+    assert x.dtype == torch.bfloat16 and x.is_contiguous()
+    b, cin, h, w = x.shape
+    y = _infer_out(x, cout, y, out_bf16)
+    _C.check(_C.lib().sassd_conv2d_bf16_infer_fwd(_C.ptr(x), _C.ptr(w_packed), _C.ptr(scale), _C.ptr(shift), 1 if relu else 0,
+                                                  _C.ptr(y), 1 if out_bf16 else 0, b, cin, cout, h, w, _C.stream()),
+             "sassd_conv2d_bf16_infer_fwd")
+    return y
+
+
+def conv1x1_bf16_infer_supported(cin, cout, hw):
+    return bool(_C.lib().sassd_conv1x1_bf16_infer_supported(cin, cout, hw))
+
+
+def conv1x1_bf16_infer_fwd(x, w_packed, cout, scale, shift, relu, y=None, out_bf16=True):
+    """1x1 conv of a bf16 NCHW map (weights from conv1x1_bf16_pack_weight), epilogue as conv2d_bf16_infer_fwd."""
+    _chk_cuda(x, w_packed)
+    assert x.dtype == torch.bfloat16 and x.is_contiguous()
+    b, cin, h, w = x.shape
+    y = _infer_out(x, cout, y, out_bf16)
+    _C.check(_C.lib().sassd_conv1x1_bf16_infer_fwd(_C.ptr(x), _C.ptr(w_packed), _C.ptr(scale), _C.ptr(shift), 1 if relu else 0,
+                                                   _C.ptr(y), 1 if out_bf16 else 0, b, cin, cout, h * w, _C.stream()),
+             "sassd_conv1x1_bf16_infer_fwd")
     return y
 
 

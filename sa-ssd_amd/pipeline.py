@@ -16,6 +16,13 @@ Stages / reference lines:
   guided anchors       ssd_rotate_head.py:307-372                       sassd_decode_filter
   PSWarp               ssd_rotate_head.py:416-447                       sassd_conv2d_fwd x2 + sassd_pswarp_sample
   rescore + NMS        ssd_rotate_head.py:487-533                       sassd_rescore_nms
+
+precision="bf16" runs every dense conv (densify, BEVNet x8, the fused head, both part-sensitive convs) on bf16 operands with
+fp32 accumulation: sassd_densify_bf16, sassd_conv2d_bf16_infer_fwd (3x3), sassd_conv1x1_bf16_infer_fwd (1x1).  The weights are
+the raw conv weights rounded once at construction (BatchNorm is not folded into them: it is applied in fp32 to the
+accumulator, relu(acc * scale + shift)), and the maps between two dense convs are stored as bf16 -- rounding at the store is
+the rounding the consumer would apply at its load.  Everything else (voxelizer, rulebooks, sparse convs, anchor mask, decode,
+PSWarp sampling, rescore / NMS) and the head / part-sensitive outputs it reads stay fp32.
 """
 import numpy as np
 
@@ -48,6 +55,15 @@ def fold_bn(sd, prefix, eps=BN_EPS):
     return scale.contiguous(), (b - m * scale).contiguous()
 
 
+def _bev_weight(sd, i, D3):
+    w = sd["neck.fcn.conv%d.weight" % i].float()
+    if i == 0:      # densify writes d-major channels (d*C + c); reference order is c*D + d (cmn.py:113-114)
+        cout, cin = w.shape[:2]
+        c = cin // D3
+        w = w.view(cout, c, D3, 3, 3).permute(0, 2, 1, 3, 4).reshape(cout, cin, 3, 3)
+    return w.contiguous()
+
+
 class InferencePlan:
     """Pre-packed weights + pre-allocated buffers for a fixed (batch_size, config)."""
 
@@ -57,7 +73,13 @@ class InferencePlan:
                  anchors_per_loc=2, grid_offsets=(0., 40.), featmap_stride=0.4, rpn_thr=0.1, score_thr=0.3,
                  iou_thr=0.1, cap_k=4096, cap_d=512, device=None, level_cap_factor=2, overlap=True, winograd=True,
                  fused_rulebooks=True, chain_bev=True, pyramid_persistent=False, spconv_cfg=None, wino4_cfg=None,
-                 skip_inactive_tiles=True, rb_sync_levels=(0, 1, 2, 3), ps_tail=False):
+                 skip_inactive_tiles=True, rb_sync_levels=(0, 1, 2, 3), ps_tail=False, precision="fp32"):
+        """precision: "fp32" (default) or "bf16" (module docstring).  In bf16 mode the fp32 kernel-selection knobs
+        (winograd, chain_bev, wino4_cfg, ps_tail, skip_inactive_tiles) are ignored, and a shape the bf16 kernels do not
+        support raises ValueError here (there is no fp32 fall-back)."""
+        if precision not in ("fp32", "bf16"):
+            raise ValueError("precision must be 'fp32' or 'bf16', got %r" % (precision,))
+        self.precision, self.bf16 = precision, precision == "bf16"
         dev = torch.device(device if device is not None else "cuda:0")
         self.dev, self.B, self.ncls, self.A = dev, int(batch_size), int(num_class), int(anchors_per_loc)
         self.voxel_size = np.asarray(voxel_size, np.float32)
@@ -89,13 +111,99 @@ class InferencePlan:
             self.sp.append((kind, cin, cout, key, wp, scale, shift))
 
         # ---- dense weights ------------------------------------------------------------------------
+        hw = torch.cat([sd["rpn_head.conv_box.weight"], sd["rpn_head.conv_cls.weight"],
+                        sd["rpn_head.conv_dir_cls.weight"]], 0).float().contiguous()
+        hb = torch.cat([sd["rpn_head.conv_box.bias"], sd["rpn_head.conv_cls.bias"],
+                        sd["rpn_head.conv_dir_cls.bias"]], 0).float().contiguous()
+        self.n_box = sd["rpn_head.conv_box.weight"].shape[0]
+        self.n_cls = sd["rpn_head.conv_cls.weight"].shape[0]
+        self.n_dir = sd["rpn_head.conv_dir_cls.weight"].shape[0]
+        self.head_c = hw.shape[0]
+        self.head_b = hb
+        w0 = sd["extra_head.convs.0.weight"].float().contiguous()
+        self.ps_parts = w0.shape[0]
+        self.ps_s0, self.ps_b0 = fold_bn(sd, "extra_head.convs.1")
+        w1 = sd["extra_head.convs.3.weight"].float().contiguous()
+        if self.bf16:
+            self._dense_weights_bf16(sd, hw, w0, w1)
+        else:
+            self._dense_weights_fp32(sd, hw, w0, w1, winograd, chain_bev, wino4_cfg, ps_tail)
+
+        # ---- anchors --------------------------------------------------------------------------------
+        self.Atot = self.ncls * self.H * self.W * self.A
+        if anchors is not None:
+            an = np.asarray(anchors, np.float32).reshape(-1, 7)
+            assert an.shape[0] == self.Atot, (an.shape, self.Atot)
+            self.anchors = torch.from_numpy(np.ascontiguousarray(an)).to(dev)
+            bv = anchors_bv if anchors_bv is not None else A.rbbox2d_to_near_bbox(an[:, [0, 1, 3, 4, 6]])
+            self.anchors_bv = torch.from_numpy(np.ascontiguousarray(bv, np.float32)).to(dev)
+        else:
+            self.anchors = self.anchors_bv = None
+
+        # ---- buffers --------------------------------------------------------------------------------
+        B, H, W = self.B, self.H, self.W
+        i32, f32 = torch.int32, torch.float32
+        z = lambda *s, dt=f32: torch.zeros(*s, dtype=dt, device=dev)       # noqa: E731
+        self.status = z(1, dt=i32)
+        self.row_off = z(B + 1, dt=i32)
+        self.vnum = z(B, dt=i32)
+        self.n = [self.row_off[B:B + 1]] + [z(1, dt=i32) for _ in range(3)]       # device row counts per level
+        self.idx = [z(c, 4, dt=i32) for c in self.caps]
+        self.tables = [K.HashTable(c, dev) for c in self.caps]
+        self.nbr = {key: z(self.caps[lvl], 27, dt=i32)
+                    for key, lvl in (("subm0", 0), ("down0", 1), ("subm1", 1), ("down1", 2), ("subm2", 2),
+                                     ("down2", 3), ("subm3", 3))}
+        self.feat = [z(max(self.caps), 64), z(max(self.caps), 64)]
+        self.mean = z(self.caps[0], 4)
+        mdt = torch.bfloat16 if self.bf16 else f32          # maps read by a dense conv (bf16 mode: rounded at the store)
+        self.dense = z(B, 64 * D3, H, W, dt=mdt)
+        self.act = [z(B, 256, H, W, dt=mdt) for _ in range(3)]
+        self.head_out = z(B, self.head_c, H, W)
+        self.ps_t = [z(B, self.ps_parts, H, W, dt=mdt), z(B, self.ps_parts, H, W)]
+        self.mask = z(B, self.Atot, dt=torch.uint8)
+        self.df = dict(guided=z(B, self.capK, 7), labels=z(B, self.capK, dt=i32), scores=z(B, self.capK),
+                       counts=z(B, dt=i32))
+        self.logits = z(B, self.capK)
+        self.det = dict(boxes=z(B, self.capD, 7), scores=z(B, self.capD), labels=z(B, self.capD, dt=i32),
+                        counts=z(B, dt=i32))
+        self.middle = {}
+        # all seven rulebooks through the fused pyramid (1 fill + 8 launches); the per-op chain (30) stays selectable for A/B
+        self.pyr = None
+        if fused_rulebooks:
+            self.pyr = K.RulebookPyramid(self.idx, self.n, self.caps, self.shape0, B,
+                                         [self.nbr["subm%d" % l] for l in range(4)],
+                                         [None] + [self.nbr["down%d" % l] for l in range(3)], self.status)
+        # True: the whole pyramid as ONE persistent launch (in-launch grid barriers) instead of two launches per level
+        self.pyramid_persistent = bool(pyramid_persistent)
+        # per-call kernel-selection words of the C ABI (None: the binding's default, 0 in production)
+        self.spconv_cfg, self.wino4_cfg = spconv_cfg, wino4_cfg
+        self.graph = None
+        self._wsid = id(self)
+        # coordinate-only work (rulebooks, anchors_mask) runs on a side stream, overlapping the feature path
+        self.overlap = bool(overlap)
+        self.side = torch.cuda.Stream(device=dev) if self.overlap else None
+        self.rb_ev = {k: torch.cuda.Event() for k in self.nbr}
+        self.mask_ev = torch.cuda.Event()
+        # BEV conv0 reads the densified sparse map: its Winograd launch runs on the tiles that have an occupied pixel in their
+        # 6x6 patch only (56 % on a KITTI frame; bit-identical, the others' products are exactly zero).  The map is built from
+        # the level-3 coordinates on the side stream.
+        self.tile_map = None
+        if skip_inactive_tiles and not self.bf16 and self.bev[0][5] == 4:
+            n_ints = K._C.lib().sassd_wino4_tile_map_ints(B, H, W)
+            if n_ints:
+                self.tile_map = z(n_ints, dt=i32)
+        self.tmap_ev = torch.cuda.Event()
+        self.rb_sync_levels = tuple(sorted(int(l) for l in rb_sync_levels))   # levels whose completion the main stream waits
+        assert self.rb_sync_levels and self.rb_sync_levels[-1] == 3           # for ((0, 1, 2, 3): one wait per level)
+        self.prof = None           # set to {} to collect (name, start_event, end_event) tuples per frame
+
+    def _dense_weights_fp32(self, sd, hw, w0, w1, winograd, chain_bev, wino4_cfg, ps_tail):
+        """precision="fp32": BEVNet on Winograd / fp32-MFMA kernels with BatchNorm folded into the epilogues, the heads on the
+        narrow / direct fp32 kernels."""
+        D3, dev = self.D3, self.dev
         self.bev = []
         for i in range(8):
-            w = sd["neck.fcn.conv%d.weight" % i].float()
-            if i == 0:      # densify writes d-major channels (d*C + c); reference order is c*D + d (cmn.py:113-114)
-                cout, cin = w.shape[:2]
-                c = cin // D3
-                w = w.view(cout, c, D3, 3, 3).permute(0, 2, 1, 3, 4).reshape(cout, cin, 3, 3)
+            w = _bev_weight(sd, i, D3)
             scale, shift = fold_bn(sd, "neck.fcn.bn%d" % i)
             # 3x3 layers: Winograd F(4x4,3x3) (transform + 36 MFMA GEMMs + transform: 4x fewer multiplications) when the
             # shape allows, else the fused F(2x2,3x3) kernel (2.25x fewer), else the direct kernel.  `winograd` = 2
@@ -125,21 +233,10 @@ class InferencePlan:
                 self.chain[i] = bool(chain_bev and self.bev[i][5] == 4 and self.bev[i - 1][5] == 4 and i - 1 != 6 and
                                      self.bev[i - 1][1] == self.bev_cin[i] and self.bev[i - 1][1] == self.bev[i][1] and
                                      K.conv2d_wino4_chain_supported(self.bev_cin[i], self.bev[i][1], self.H, self.W))
-        hw = torch.cat([sd["rpn_head.conv_box.weight"], sd["rpn_head.conv_cls.weight"],
-                        sd["rpn_head.conv_dir_cls.weight"]], 0).float().contiguous()
-        hb = torch.cat([sd["rpn_head.conv_box.bias"], sd["rpn_head.conv_cls.bias"],
-                        sd["rpn_head.conv_dir_cls.bias"]], 0).float().contiguous()
-        self.n_box = sd["rpn_head.conv_box.weight"].shape[0]
-        self.n_cls = sd["rpn_head.conv_cls.weight"].shape[0]
-        self.n_dir = sd["rpn_head.conv_dir_cls.weight"].shape[0]
-        self.head_c = hw.shape[0]
         # 1x1 convs with <= 32 output channels (the single-class fused head, the second part-sensitive conv) stream on the
         # vector ALU (sassd_conv1x1_narrow_fwd); wider ones (three-class head: 60 maps) stay on the MFMA kernel
         self.head_narrow = K.conv1x1_narrow_supported(hw.shape[1], hw.shape[0])
         self.head_w = K.conv1x1_narrow_pack_weight(hw) if self.head_narrow else K.conv2d_pack_weight(hw)
-        self.head_b = hb
-        w0 = sd["extra_head.convs.0.weight"].float().contiguous()
-        self.ps_parts = w0.shape[0]
         self.ps_w0 = K.conv2d_pack_weight(w0)
         # the part-sensitive 3x3 conv (256 -> 28) as a narrow TAIL of the Winograd chain on conv6's products (fused transform +
         # 64-channel GEMM block + output transform; conv6's own NCHW map is stored by the fused transform): when conv6 is a
@@ -149,77 +246,42 @@ class InferencePlan:
         self.ps_tail = bool(ps_tail and chain_bev and self.bev[6][5] == 4 and self.chain[6] and self.ps_parts <= 64 and
                             w0.shape[2] == 3 and w0.shape[1] == self.bev[6][1] and not ((wino4_cfg or 0) & 0xff))
         self.ps_w0t = K.conv2d_wino4_pack_weight_narrow(w0) if self.ps_tail else None
-        self.ps_s0, self.ps_b0 = fold_bn(sd, "extra_head.convs.1")
-        w1 = sd["extra_head.convs.3.weight"].float().contiguous()
         self.ps_narrow = K.conv1x1_narrow_supported(w1.shape[1], w1.shape[0])
         self.ps_w1 = K.conv1x1_narrow_pack_weight(w1) if self.ps_narrow else K.conv2d_pack_weight(w1)
 
-        # ---- anchors --------------------------------------------------------------------------------
-        self.Atot = self.ncls * self.H * self.W * self.A
-        if anchors is not None:
-            an = np.asarray(anchors, np.float32).reshape(-1, 7)
-            assert an.shape[0] == self.Atot, (an.shape, self.Atot)
-            self.anchors = torch.from_numpy(np.ascontiguousarray(an)).to(dev)
-            bv = anchors_bv if anchors_bv is not None else A.rbbox2d_to_near_bbox(an[:, [0, 1, 3, 4, 6]])
-            self.anchors_bv = torch.from_numpy(np.ascontiguousarray(bv, np.float32)).to(dev)
-        else:
-            self.anchors = self.anchors_bv = None
+    def _dense_weights_bf16(self, sd, hw, w0, w1):
+        """precision="bf16": the raw weights of every dense conv rounded once into bf16 packs (BatchNorm stays out of them),
+        after checking that the bf16 inference kernels take every shape of the frame."""
+        H, W = self.H, self.W
 
-        # ---- buffers --------------------------------------------------------------------------------
-        B, H, W = self.B, self.H, self.W
-        i32, f32 = torch.int32, torch.float32
-        z = lambda *s, dt=f32: torch.zeros(*s, dtype=dt, device=dev)       # noqa: E731
-        self.status = z(1, dt=i32)
-        self.row_off = z(B + 1, dt=i32)
-        self.vnum = z(B, dt=i32)
-        self.n = [self.row_off[B:B + 1]] + [z(1, dt=i32) for _ in range(3)]       # device row counts per level
-        self.idx = [z(c, 4, dt=i32) for c in self.caps]
-        self.tables = [K.HashTable(c, dev) for c in self.caps]
-        self.nbr = {key: z(self.caps[lvl], 27, dt=i32)
-                    for key, lvl in (("subm0", 0), ("down0", 1), ("subm1", 1), ("down1", 2), ("subm2", 2),
-                                     ("down2", 3), ("subm3", 3))}
-        self.feat = [z(max(self.caps), 64), z(max(self.caps), 64)]
-        self.mean = z(self.caps[0], 4)
-        self.dense = z(B, 64 * D3, H, W)
-        self.act = [z(B, 256, H, W) for _ in range(3)]
-        self.head_out = z(B, self.head_c, H, W)
-        self.ps_t = [z(B, self.ps_parts, H, W), z(B, self.ps_parts, H, W)]
-        self.mask = z(B, self.Atot, dt=torch.uint8)
-        self.df = dict(guided=z(B, self.capK, 7), labels=z(B, self.capK, dt=i32), scores=z(B, self.capK),
-                       counts=z(B, dt=i32))
-        self.logits = z(B, self.capK)
-        self.det = dict(boxes=z(B, self.capD, 7), scores=z(B, self.capD), labels=z(B, self.capD, dt=i32),
-                        counts=z(B, dt=i32))
-        self.middle = {}
-        # all seven rulebooks through the fused pyramid (1 fill + 8 launches); the per-op chain (30) stays selectable for A/B
-        self.pyr = None
-        if fused_rulebooks:
-            self.pyr = K.RulebookPyramid(self.idx, self.n, self.caps, self.shape0, B,
-                                         [self.nbr["subm%d" % l] for l in range(4)],
-                                         [None] + [self.nbr["down%d" % l] for l in range(3)], self.status)
-        # True: the whole pyramid as ONE persistent launch (in-launch grid barriers) instead of two launches per level
-        self.pyramid_persistent = bool(pyramid_persistent)
-        # per-call kernel-selection words of the C ABI (None: the binding's default, 0 in production)
-        self.spconv_cfg, self.wino4_cfg = spconv_cfg, wino4_cfg
-        self.graph = None
-        self._wsid = id(self)
-        # coordinate-only work (rulebooks, anchors_mask) runs on a side stream, overlapping the feature path
-        self.overlap = bool(overlap)
-        self.side = torch.cuda.Stream(device=dev) if self.overlap else None
-        self.rb_ev = {k: torch.cuda.Event() for k in self.nbr}
-        self.mask_ev = torch.cuda.Event()
-        # BEV conv0 reads the densified sparse map: its Winograd launch runs on the tiles that have an occupied pixel in their
-        # 6x6 patch only (56 % on a KITTI frame; bit-identical, the others' products are exactly zero).  The map is built from
-        # the level-3 coordinates on the side stream.
-        self.tile_map = None
-        if skip_inactive_tiles and self.bev[0][5] == 4:
-            n_ints = K._C.lib().sassd_wino4_tile_map_ints(B, H, W)
-            if n_ints:
-                self.tile_map = z(n_ints, dt=i32)
-        self.tmap_ev = torch.cuda.Event()
-        self.rb_sync_levels = tuple(sorted(int(l) for l in rb_sync_levels))   # levels whose completion the main stream waits
-        assert self.rb_sync_levels and self.rb_sync_levels[-1] == 3           # for ((0, 1, 2, 3): one wait per level)
-        self.prof = None           # set to {} to collect (name, start_event, end_event) tuples per frame
+        def need(ok, what):
+            if not ok:
+                raise ValueError("precision='bf16': %s on a %dx%d BEV map is not supported by the bf16 inference kernels"
+                                 % (what, H, W))
+        need(K.densify_bf16_supported(64, self.shapes[3]), "the dense map (64 x %d channels)" % self.D3)
+        self.bev, self.chain, self.wino4_ws, self.ps_tail, self.ps_w0t = [], [False] * 8, None, False, None
+        self.head_narrow = self.ps_narrow = False
+        self.bev_cin = [int(sd["neck.fcn.conv%d.weight" % i].shape[1]) for i in range(8)]
+        self.bev16 = []
+        for i in range(8):
+            w = _bev_weight(sd, i, self.D3)
+            cout, cin, k = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
+            if k == 3:
+                need(K.conv2d_bf16_infer_supported(cin, cout, H, W), "BEV conv%d (3x3, %d -> %d)" % (i, cin, cout))
+                wp = K.conv2d_bf16_infer_pack_weight(w)
+            else:
+                need(k == 1 and K.conv1x1_bf16_infer_supported(cin, cout, H * W),
+                     "BEV conv%d (%dx%d, %d -> %d)" % (i, k, k, cin, cout))
+                wp = K.conv1x1_bf16_pack_weight(w)
+            scale, shift = fold_bn(sd, "neck.fcn.bn%d" % i)
+            self.bev16.append((wp, cout, k, scale, shift))
+        need(K.conv1x1_bf16_infer_supported(hw.shape[1], hw.shape[0], H * W), "the fused SSD head (%d -> %d)" % (hw.shape[1], hw.shape[0]))
+        self.head_w = K.conv1x1_bf16_pack_weight(hw)
+        need(w0.shape[2] == 3 and K.conv2d_bf16_infer_supported(w0.shape[1], w0.shape[0], H, W),
+             "the part-sensitive conv (%d -> %d)" % (w0.shape[1], w0.shape[0]))
+        self.ps_w0 = K.conv2d_bf16_infer_pack_weight(w0)
+        need(K.conv1x1_bf16_infer_supported(w1.shape[1], w1.shape[0], H * W), "the part-sensitive 1x1 (%d -> %d)" % (w1.shape[1], w1.shape[0]))
+        self.ps_w1 = K.conv1x1_bf16_pack_weight(w1)
 
     def _ev(self):
         e = torch.cuda.Event(enable_timing=True)
@@ -350,10 +412,15 @@ class InferencePlan:
         if not densify:
             return
         e1 = self._ev() if self.prof is not None else None
-        K.densify(x, self.idx[3], self.n[3], self.caps[3], self.shapes[3], self.B, 1, self.dense)
+        if self.bf16:
+            K.densify_bf16(x, self.idx[3], self.n[3], self.caps[3], self.shapes[3], self.B, 1, self.dense)
+        else:
+            K.densify(x, self.idx[3], self.n[3], self.caps[3], self.shapes[3], self.B, 1, self.dense)
         self._seg("densify", e1)
 
     def bev_and_heads(self):
+        if self.bf16:
+            return self._bev_and_heads_bf16()
         x = self.dense
         for i, (wp, cout, ks, scale, shift, wino) in enumerate(self.bev):
             y = self.act[i % 2] if i < 7 else self.act[2]
@@ -387,6 +454,7 @@ class InferencePlan:
             if i == 6:
                 self.conv6 = y
         self.x = x
+        e0 = self._ev() if self.prof is not None else None
         if self.head_narrow:
             K.conv1x1_narrow_fwd(x, self.head_w, self.head_c, None, self.head_b, False, self.head_out)
         else:
@@ -397,6 +465,27 @@ class InferencePlan:
             K.conv1x1_narrow_fwd(self.ps_t[0], self.ps_w1, self.ps_parts, None, None, False, self.ps_t[1])
         else:
             K.conv2d_fwd(self.ps_t[0], self.ps_w1, self.ps_parts, 1, None, None, False, self.ps_t[1])
+        self._seg("heads", e0)
+
+    def _bev_and_heads_bf16(self):
+        x = self.dense
+        for i, (wp, cout, ks, scale, shift) in enumerate(self.bev16):
+            y = self.act[i % 2] if i < 7 else self.act[2]
+            e0 = self._ev() if self.prof is not None else None
+            if ks == 3:
+                K.conv2d_bf16_infer_fwd(x, wp, cout, scale, shift, True, y)
+            else:
+                K.conv1x1_bf16_infer_fwd(x, wp, cout, scale, shift, True, y)
+            self._seg("bev_conv%d" % i, e0)
+            x = y
+            if i == 6:
+                self.conv6 = y
+        self.x = x
+        e0 = self._ev() if self.prof is not None else None
+        K.conv1x1_bf16_infer_fwd(x, self.head_w, self.head_c, None, self.head_b, False, self.head_out, out_bf16=False)
+        K.conv2d_bf16_infer_fwd(self.conv6, self.ps_w0, self.ps_parts, self.ps_s0, self.ps_b0, True, self.ps_t[0])
+        K.conv1x1_bf16_infer_fwd(self.ps_t[0], self.ps_w1, self.ps_parts, None, None, False, self.ps_t[1], out_bf16=False)
+        self._seg("heads", e0)
 
     def anchor_masks(self, masks=None):
         if masks is not None:
