@@ -700,6 +700,47 @@ int sassd_adam_step(float *param, const float *grad, float *exp_avg, float *exp_
                     const float *grad_sumsq, float lr, float beta1, float beta2, float eps, float weight_decay,
                     int step, float max_norm, float grad_scale, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Deterministic training (opt-in: train_cfg['deterministic'] or torch.use_deterministic_algorithms(True)).
+ * The default training path sums four gradients with float atomics, so two runs of the same seeded workload differ in
+ * the last bits and drift apart over many steps.  These `_det` twins fix every summation order, so that a step is
+ * bit-reproducible and a CPU model can recompute their results bit for bit.  The mode switches exactly these launches:
+ * the aux-head scatter (sassd_aux_head_bwd), the PSWarp backward (sassd_pswarp_sample_bwd), the gradient-norm square
+ * sum of the clip (sassd_grad_sumsq) and the reference-surface three_interpolate_grad.  Everything else on the training
+ * path already reduces in a fixed order.  The twins contain no float atomics; their integer atomics only count list
+ * lengths or place entries that are sorted afterwards.  They issue no hipMemsetAsync (capture-safe).
+ *
+ * 3-NN interpolation gradient (sassd_three_interpolate_grad_det; sassd_aux_head_bwd_det per level):
+ *   grad[r, ch] = the value on entry (0 for the aux head, grad_points as passed for three_interpolate_grad), then
+ *   t = fl(g[p, ch] * w[p, j]) added one at a time, fl(acc + t), for every (p, j) with idx[p, j] == r in ascending
+ *   (p, j) order.  fp32, each product rounded before it is added (no FMA contraction).  Each (row, channel) sum is
+ *   sequential; only rows and channels run in parallel.  Entries with idx outside [0, m) are ignored.  For the aux head,
+ *   g = d(interpolated features) of the point pass and w the interpolation weights of the forward.  dw1 / dw2 of
+ *   sassd_aux_head_bwd_det are bit-identical to sassd_aux_head_bwd's (already a fixed-order reduction).
+ * PSWarp backward (sassd_pswarp_sample_bwd_det): dfeat[b, k, y, x] = its value on entry, then the tap values of
+ *   sassd_pswarp_sample_bwd for that pixel (go * wx * wy, evaluated left to right) added in ascending box index over
+ *   boxes < min(counts[b], capK).  dguided is bit-identical to sassd_pswarp_sample_bwd's.  Any capK (the taps are sorted
+ *   in LDS 512 boxes at a time); the workspace query returns 0 today and ws may then be NULL.
+ * Gradient square sum (sassd_grad_sumsq_det): the summation order depends on n only (not on CU count, occupancy or
+ *   launch timing): min(1024, max(1, ceil(n / 1024))) block partials in fp32 (optim.hip spells out the order), summed
+ *   by one workgroup in double.  *out is WRITTEN, not accumulated.  Within 1e-6 relative of a float64 sum.
+ * Workspaces are caller-owned, sized by the queries (host arithmetic; 0 for impossible shapes); short -> SASSD_ENOSPC. */
+size_t sassd_three_interpolate_grad_det_workspace_bytes(int n, int m);
+int sassd_three_interpolate_grad_det(int c, int n, int m, const float *grad_out, const int32_t *idx,
+                                     const float *weight, float *grad_points, void *ws, size_t ws_bytes, void *stream);
+size_t sassd_aux_head_bwd_det_workspace_bytes(int N, const int *M);
+int sassd_aux_head_bwd_det(int N, const float *const *feats, const int *M, const int32_t *const *nn_idx,
+                           const float *w1, const float *w2, const float *wgt, const float *h, const float *gout,
+                           const float *grad_sums, float *const *grad_feats, float *dw1, float *dw2, void *workspace,
+                           size_t workspace_bytes, void *stream);
+size_t sassd_pswarp_sample_bwd_det_workspace_bytes(int batch, int capK);
+int sassd_pswarp_sample_bwd_det(const float *feat, int batch, int H, int W, const float *guided,
+                                const int32_t *counts, int capK, float grid_off_x, float grid_off_y,
+                                float spatial_scale, const float *dlogits, float *dfeat, float *dguided, void *ws,
+                                size_t ws_bytes, void *stream);
+size_t sassd_grad_sumsq_det_workspace_bytes(long n);
+int sassd_grad_sumsq_det(const float *grad, long n, float *out, void *ws, size_t ws_bytes, void *stream);
+
 /* Hardware self-test helper used by tests: D = A(32x2k) * B(2k x32) through v_mfma_f32_32x32x2_f32 and
  * D = A(16x4k) * B(4k x16) through v_mfma_f32_16x16x4_f32 with the lane maps the kernels assume. */
 int sassd_mfma_probe(const float *a32, const float *b32, float *d32, const float *a16, const float *b16,

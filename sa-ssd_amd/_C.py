@@ -166,6 +166,15 @@ _SIGS = {
     "sassd_grad_sumsq": (_I, [_P, C.c_long, _P, _P]),
     "sassd_adam_step": (_I, [_P, _P, _P, _P, C.c_long, _P, _F, _F, _F, _F, _F, _I, _F, _F, _P]),
     "sassd_mfma_probe": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
+    # deterministic training mode (include/sassd.h "Deterministic training")
+    "sassd_three_interpolate_grad_det_workspace_bytes": (_SZ, [_I, _I]),
+    "sassd_three_interpolate_grad_det": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    "sassd_aux_head_bwd_det_workspace_bytes": (_SZ, [_I, _P]),
+    "sassd_aux_head_bwd_det": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "sassd_pswarp_sample_bwd_det_workspace_bytes": (_SZ, [_I, _I]),
+    "sassd_pswarp_sample_bwd_det": (_I, [_P, _I, _I, _I, _P, _P, _I, _F, _F, _F, _P, _P, _P, _P, _SZ, _P]),
+    "sassd_grad_sumsq_det_workspace_bytes": (_SZ, [C.c_long]),
+    "sassd_grad_sumsq_det": (_I, [_P, C.c_long, _P, _P, _SZ, _P]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

@@ -351,7 +351,7 @@ class PSWarpFn(Function):
     """Part-sensitive bilinear sampling of one sample: feat [1,28,H,W], boxes [K,7] -> logits [K]."""
 
     @staticmethod
-    def forward(ctx, feat, boxes, grid_offsets, spatial_scale):
+    def forward(ctx, feat, boxes, grid_offsets, spatial_scale, deterministic=False):
         k = boxes.shape[0]
         feat = feat.contiguous()
         boxes = boxes.contiguous()
@@ -359,6 +359,7 @@ class PSWarpFn(Function):
         lg = K.pswarp_sample(feat, boxes.view(1, k, 7), cnt, k, grid_offsets, spatial_scale)
         ctx.save_for_backward(feat, boxes)
         ctx.args = (grid_offsets, spatial_scale)
+        ctx.deterministic = bool(deterministic)
         return lg.view(-1)
 
     @staticmethod
@@ -367,8 +368,8 @@ class PSWarpFn(Function):
         k = boxes.shape[0]
         cnt = _n_ptr(k, feat.device)
         dfeat, dg = K.pswarp_sample_bwd(feat, boxes.view(1, k, 7), cnt, k, ctx.args[0], ctx.args[1],
-                                        dlog.contiguous().view(1, k))
-        return dfeat, dg.view(k, 7), None, None
+                                        dlog.contiguous().view(1, k), deterministic=ctx.deterministic)
+        return dfeat, dg.view(k, 7), None, None, None
 
 
 class RpnLossFn(Function):
@@ -395,18 +396,20 @@ class PSWarpBatchFn(Function):
     (device) -> logits [B,capK], zero for the rows past a sample's count (their gradients are zero too)."""
 
     @staticmethod
-    def forward(ctx, feat, boxes, counts, grid_offsets, spatial_scale):
+    def forward(ctx, feat, boxes, counts, grid_offsets, spatial_scale, deterministic=False):
         feat, boxes = feat.contiguous(), boxes.contiguous()
         lg = K.pswarp_sample(feat, boxes, counts, boxes.shape[1], grid_offsets, spatial_scale)
         ctx.save_for_backward(feat, boxes, counts)
         ctx.args = (grid_offsets, spatial_scale)
+        ctx.deterministic = bool(deterministic)
         return lg
 
     @staticmethod
     def backward(ctx, dlog):
         feat, boxes, counts = ctx.saved_tensors
-        dfeat, dg = K.pswarp_sample_bwd(feat, boxes, counts, boxes.shape[1], ctx.args[0], ctx.args[1], dlog.contiguous())
-        return dfeat, dg, None, None, None
+        dfeat, dg = K.pswarp_sample_bwd(feat, boxes, counts, boxes.shape[1], ctx.args[0], ctx.args[1], dlog.contiguous(),
+                                        deterministic=ctx.deterministic)
+        return dfeat, dg, None, None, None, None
 
 
 class BnReluFn(Function):
@@ -560,24 +563,27 @@ class AuxHeadFn(Function):
     """The auxiliary head's interpolation + three Linear layers + both loss sums in one forward kernel, and its whole
     backward (feature gradients of the three scales, weight gradients) in three (sassd_aux_head_fwd / _bwd).
     Inputs: the three middle feature tensors [M_s, C_s], point_fc / point_cls / point_reg weights, then the
-    non-differentiable context (3-NN indices / squared distances per scale, labels, targets, positive count).
+    non-differentiable context (3-NN indices / squared distances per scale, labels, targets, positive count) and the
+    deterministic-mode flag (sassd_aux_head_bwd_det in the backward).
     -> loss sums [2] = (focal, smooth-L1), both already divided by max(#positive points, 1)."""
 
     @staticmethod
-    def forward(ctx, f0, f1, f2, w_fc, w_cls, w_reg, nn_idx, nn_d2, label, target, npos):
+    def forward(ctx, f0, f1, f2, w_fc, w_cls, w_reg, nn_idx, nn_d2, label, target, npos, deterministic=False):
         feats = [f0.contiguous(), f1.contiguous(), f2.contiguous()]
         w1 = w_fc.detach().contiguous()
         w2 = torch.cat([w_cls.detach(), w_reg.detach()], 0).contiguous()
         sums, wgt, h, out, gout = K.aux_head_fwd(feats, nn_idx, nn_d2, w1, w2, label, target, npos)
         ctx.save_for_backward(feats[0], feats[1], feats[2], w1, w2, wgt, h, gout)
         ctx.nn_idx = nn_idx
+        ctx.deterministic = bool(deterministic)
         return sums
 
     @staticmethod
     def backward(ctx, g):
         f0, f1, f2, w1, w2, wgt, h, gout = ctx.saved_tensors
-        gf, dw1, dw2 = K.aux_head_bwd([f0, f1, f2], ctx.nn_idx, w1, w2, wgt, h, gout, g.contiguous())
-        return gf[0], gf[1], gf[2], dw1, dw2[0:1], dw2[1:4], None, None, None, None, None
+        gf, dw1, dw2 = K.aux_head_bwd([f0, f1, f2], ctx.nn_idx, w1, w2, wgt, h, gout, g.contiguous(),
+                                      deterministic=ctx.deterministic)
+        return gf[0], gf[1], gf[2], dw1, dw2[0:1], dw2[1:4], None, None, None, None, None, None
 
 
 class GuidedDecodeFn(Function):

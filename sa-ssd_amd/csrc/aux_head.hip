@@ -18,11 +18,15 @@
 //                           reference's three_interpolate_grad), one thread per (point, channel): the 64 lanes of a wave
 //                           add to CONSECUTIVE channels of one row (a first version issued the atomics from the
 //                           row-per-thread kernel, 64 different rows per instruction: 920 us instead of 60)
+//   aux_gather_det_kernel   the deterministic twin of aux_scatter_kernel (sassd_aux_head_bwd_det): an inverted index of
+//                           the three 3-NN lists (inv_index.h), then one thread per (voxel row, channel) sums its
+//                           rounded products df * w in ascending (point, neighbour) order
 //   aux_wgrad_kernel        dW1 = sum_p dh f^T, dW2 = sum_p d(out) h^T: 64-point chunks staged in LDS, each thread owns a
 //                           5 x 8 patch of dW1 and one entry of dW2; per-workgroup partials, fixed-order reduction
 // fp32 VALU throughout: on gfx950 the fp32 vector rate equals the fp32 MFMA rate, and a row-per-thread formulation needs
 // no operand shuffles.
 #include "common.h"
+#include "inv_index.h"
 
 namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -554,6 +558,119 @@ extern "C" int sassd_aux_head_bwd(int N, const float *const *feats, const int *M
     P.dfbuf = (float *)((char *)workspace + (wpart_bytes > part_bytes ? wpart_bytes : part_bytes));
     hipLaunchKernelGGL(aux_bwd_points_kernel, dim3(cdiv(N, 256)), dim3(256), 0, s, P);
     hipLaunchKernelGGL(aux_scatter_kernel, dim3((unsigned)(((size_t)N * kF + 255) / 256)), dim3(256), 0, s, P);
+    static std::atomic<unsigned long long> attr_done{0};
+    rc = sassd_dyn_lds((const void *)aux_wgrad_kernel, kWgradLds, attr_done);
+    if (rc) return rc;
+    const int nwg = aux_wgrad_wgs(N, &P.chunks_per_wg);
+    P.wpart = (float *)workspace;
+    hipLaunchKernelGGL(aux_wgrad_kernel, dim3(nwg), dim3(256), kWgradLds, s, P);
+    hipLaunchKernelGGL(aux_wgrad_reduce_kernel, dim3(cdiv(kH * kF + kOut * kH, 32)), dim3(256), 0, s,
+                       (const float *)workspace, nwg, dw1, dw2);
+    return sassd_launch_status();
+}
+
+// ---- deterministic mode (sassd_aux_head_bwd_det) ---------------------------------------------------------------------
+namespace {
+// one thread per (level-s row, channel), levels back to back; gfeat[s][r, c] = sum over the row's sorted entries of
+// fl(df[p, koff + c] * w[p, s, j]), added one at a time in list order (no contraction); rows without entries get 0
+__global__ void __launch_bounds__(256) aux_gather_det_kernel(AuxArgs P, InvIndex X)
+{
+#pragma clang fp contract(off)
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const long t1 = (long)X.M[0] * 32, t2 = t1 + (long)X.M[1] * 64, t3 = t2 + (long)X.M[2] * 64;
+    if (t >= t3) return;
+    int s, C, koff;
+    long u;
+    if (t < t1) { s = 0; C = 32; koff = 0; u = t; }
+    else if (t < t2) { s = 1; C = 64; koff = 32; u = t - t1; }
+    else { s = 2; C = 64; koff = 96; u = t - t2; }
+    const int r = (int)(u / C), c = (int)(u - (long)r * C);
+    const int R = X.row0[s] + r;
+    const int lo = X.start[R], hi = X.start[R + 1];
+    const int base = s * 3 * X.n;
+    const float *__restrict__ df = P.dfbuf + koff + c;
+    const float *__restrict__ wg = P.wgt + s * 3;
+    const int *__restrict__ lst = X.sorted;
+    float acc = 0.f;
+    int k = lo;
+    for (; k + 8 <= hi; k += 8) {                       // 8 independent loads in flight, then 8 ordered adds
+        float pr[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int e = lst[k + q] - base, p = e / 3, j = e - p * 3;
+            pr[q] = df[(size_t)p * kF] * wg[(size_t)p * 9 + j];
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) acc = acc + pr[q];
+    }
+    for (; k < hi; ++k) {
+        const int e = lst[k] - base, p = e / 3, j = e - p * 3;
+        const float pr = df[(size_t)p * kF] * wg[(size_t)p * 9 + j];
+        acc = acc + pr;
+    }
+    P.gfeat[s][(size_t)r * C + c] = acc;
+}
+
+InvIndex aux_inv_index(int N, const int *M, const int32_t *const *nn_idx)
+{
+    InvIndex X = {};
+    X.levels = 3; X.n = N; X.rows = 0;
+    for (int k = 0; k < 3; ++k) {
+        X.idx[k] = nn_idx ? nn_idx[k] : nullptr;
+        X.M[k] = M[k];
+        X.row0[k] = X.rows;
+        X.rows += M[k];
+    }
+    return X;
+}
+
+bool aux_det_shape_ok(int N, const int *M)
+{
+    if (N < 1 || !M) return false;
+    long rows = 0;
+    for (int k = 0; k < 3; ++k) {
+        if (M[k] < 1) return false;
+        rows += M[k];
+        if ((long)M[k] * 64 > (1L << 40)) return false;
+    }
+    return (long)N * 9 < (1L << 31) - 1 && rows < (1L << 31) - 1;
+}
+}  // namespace
+
+extern "C" size_t sassd_aux_head_bwd_det_workspace_bytes(int N, const int *M)
+{
+    if (!aux_det_shape_ok(N, M)) return 0;
+    return sassd_aux_head_workspace_bytes(N) + inv_index_bytes(3, N, (long)M[0] + M[1] + M[2]);
+}
+
+extern "C" int sassd_aux_head_bwd_det(int N, const float *const *feats, const int *M, const int32_t *const *nn_idx,
+                                      const float *w1, const float *w2, const float *wgt, const float *h,
+                                      const float *gout, const float *grad_sums, float *const *grad_feats, float *dw1,
+                                      float *dw2, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    AuxArgs P = {};
+    int rc = fill_common(P, N, feats, nn_idx, nullptr, w1, w2);
+    if (rc) return rc;
+    if (!M || !wgt || !h || !gout || !grad_sums || !grad_feats || !dw1 || !dw2 || !workspace) return SASSD_EINVAL;
+    if (!aux_det_shape_ok(N, M)) return SASSD_EINVAL;
+    for (int k = 0; k < 3; ++k)
+        if (!grad_feats[k]) return SASSD_EINVAL;
+    const size_t base_bytes = sassd_aux_head_workspace_bytes(N);
+    if (workspace_bytes < sassd_aux_head_bwd_det_workspace_bytes(N, M)) return SASSD_ENOSPC;
+    hipStream_t s = (hipStream_t)stream_;
+    P.wgt = (float *)wgt; P.h = (float *)h; P.gout = (float *)gout; P.gup = grad_sums;
+    for (int k = 0; k < 3; ++k) P.gfeat[k] = grad_feats[k];
+    int cpw0;
+    const size_t wpart_bytes = align_up((size_t)aux_wgrad_wgs(N, &cpw0) * (kH * kF + kOut * kH) * sizeof(float), 256);
+    const size_t part_bytes = align_up((size_t)cdiv(N, 256) * 2 * sizeof(float), 256);
+    P.dfbuf = (float *)((char *)workspace + (wpart_bytes > part_bytes ? wpart_bytes : part_bytes));
+    InvIndex X = aux_inv_index(N, M, nn_idx);
+    inv_index_carve(X, (char *)workspace + base_bytes);
+    // the index depends on nn_idx only: built first, it overlaps nothing but needs nothing from the point pass
+    inv_index_build(X, s);
+    hipLaunchKernelGGL(aux_bwd_points_kernel, dim3(cdiv(N, 256)), dim3(256), 0, s, P);
+    const long tot = (long)M[0] * 32 + (long)M[1] * 64 + (long)M[2] * 64;
+    hipLaunchKernelGGL(aux_gather_det_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, P, X);
     static std::atomic<unsigned long long> attr_done{0};
     rc = sassd_dyn_lds((const void *)aux_wgrad_kernel, kWgradLds, attr_done);
     if (rc) return rc;

@@ -178,7 +178,9 @@ __global__ void __launch_bounds__(256) pswarp_kernel(WarpParams P)
 }
 
 // backward of pswarp_kernel (training): d logits -> d feat (atomicAdd into [B,28,H,W]) and d guided [B,capK,7]
-// (the reference differentiates grid_sample w.r.t. input AND grid, so the rescoring loss also steers x,y,w,l,r)
+// (the reference differentiates grid_sample w.r.t. input AND grid, so the rescoring loss also steers x,y,w,l,r).
+// kDfeat = false: d guided only (sassd_pswarp_sample_bwd_det, whose d feat comes from pswarp_dfeat_det_kernel)
+template <bool kDfeat>
 __global__ void __launch_bounds__(256) pswarp_bwd_kernel(WarpParams P, const float *__restrict__ dlogits,
                                                          float *__restrict__ dfeat, float *__restrict__ dguided)
 {
@@ -212,10 +214,10 @@ __global__ void __launch_bounds__(256) pswarp_bwd_kernel(WarpParams P, const flo
         const bool yin0 = y0 >= 0 && y0 < P.H, yin1 = y1 >= 0 && y1 < P.H;
         float v00 = 0.f, v01 = 0.f, v10 = 0.f, v11 = 0.f;
         if (inr) {
-            if (yin0 && xin0) { v00 = im[(size_t)y0 * P.W + x0]; atomicAdd(&di[(size_t)y0 * P.W + x0], go * wx0 * wy0); }
-            if (yin0 && xin1) { v01 = im[(size_t)y0 * P.W + x1]; atomicAdd(&di[(size_t)y0 * P.W + x1], go * wx1 * wy0); }
-            if (yin1 && xin0) { v10 = im[(size_t)y1 * P.W + x0]; atomicAdd(&di[(size_t)y1 * P.W + x0], go * wx0 * wy1); }
-            if (yin1 && xin1) { v11 = im[(size_t)y1 * P.W + x1]; atomicAdd(&di[(size_t)y1 * P.W + x1], go * wx1 * wy1); }
+            if (yin0 && xin0) { v00 = im[(size_t)y0 * P.W + x0]; if (kDfeat) atomicAdd(&di[(size_t)y0 * P.W + x0], go * wx0 * wy0); }
+            if (yin0 && xin1) { v01 = im[(size_t)y0 * P.W + x1]; if (kDfeat) atomicAdd(&di[(size_t)y0 * P.W + x1], go * wx1 * wy0); }
+            if (yin1 && xin0) { v10 = im[(size_t)y1 * P.W + x0]; if (kDfeat) atomicAdd(&di[(size_t)y1 * P.W + x0], go * wx0 * wy1); }
+            if (yin1 && xin1) { v11 = im[(size_t)y1 * P.W + x1]; if (kDfeat) atomicAdd(&di[(size_t)y1 * P.W + x1], go * wx1 * wy1); }
         }
         // d sample / d fx, d fy ; fx = u, fy = v (the normalise / un-normalise pair is the identity)
         const float dfx = ((v01 - v00) * wy0 + (v11 - v10) * wy1) * go;
@@ -234,6 +236,91 @@ __global__ void __launch_bounds__(256) pswarp_bwd_kernel(WarpParams P, const flo
     if (box < K && k == 0 && dguided) {
         float *d = dguided + ((size_t)b * P.capK + box) * 7;
         d[0] = gxg; d[1] = gyg; d[2] = 0.f; d[3] = gw; d[4] = gl; d[5] = 0.f; d[6] = gr;
+    }
+}
+
+// Deterministic d feat of the PSWarp backward (sassd_pswarp_sample_bwd_det): one workgroup per (b, k) plane.  Boxes in
+// chunks of kPwChunk, ascending: the chunk's taps (pixel, box, value = go * wx * wy exactly as pswarp_bwd_kernel forms them)
+// are bitonic-sorted by (pixel, box) in LDS, then the first tap of every pixel run reads dfeat once, adds the run's values
+// in ascending box order and writes it back.  A box's 28 samples hit a pixel of plane k at most once per box, so the
+// (pixel, box) order is total; chunks follow each other (fence + barrier), so every pixel receives its taps in ascending
+// box order across the whole list, on top of the value dfeat held on entry.  No float atomics; no capK limit.
+constexpr int kPwChunk = 512;                                           // 2048 taps: 16 KB keys + 8 KB values of LDS
+
+__global__ void __launch_bounds__(256) pswarp_dfeat_det_kernel(WarpParams P, const float *__restrict__ dlogits,
+                                                               float *__restrict__ dfeat)
+{
+    __shared__ unsigned long long key[4 * kPwChunk];
+    __shared__ float val[4 * kPwChunk];
+    const int plane = blockIdx.x;
+    const int b = plane / 28, k = plane - b * 28;
+    const int K = min(P.counts[b], P.capK);
+    const int ix = k / 7, iy = k - ix * 7;
+    const size_t HW = (size_t)P.H * P.W;
+    float *di = dfeat + (size_t)plane * HW;
+    for (int c0 = 0; c0 < K; c0 += kPwChunk) {
+        const int nb = min(kPwChunk, K - c0), ne = 4 * nb;
+        const int P2 = 1 << (32 - __clz(ne - 1));
+        for (int i = threadIdx.x; i < nb; i += 256) {
+            const int box = c0 + i;
+            unsigned long long kk[4] = {~0ull, ~0ull, ~0ull, ~0ull};
+            float vv[4] = {0.f, 0.f, 0.f, 0.f};
+            // ---- the tap geometry of pswarp_bwd_kernel, statement for statement (same rounding) ----
+            const float *g = P.guided + ((size_t)b * P.capK + box) * 7;
+            const float xg = g[0], yg = g[1], wg = g[3], lg = g[4], rg = g[6];
+            const float ct = cosf(rg), st = sinf(rg);
+            const float xx = P.lin4[ix] * wg, yy = P.lin7[iy] * lg;
+            const float x = xx * ct + yy * st + xg;
+            const float y = yy * ct - xx * st + yg;
+            const float u = (x + P.offx) * P.scale, v = (y + P.offy) * P.scale;
+            const float gx = u / (float)(P.W - 1) * 2.f - 1.f, gy = v / (float)(P.H - 1) * 2.f - 1.f;
+            float fx = (gx + 1.f) / 2.f * (float)(P.W - 1), fy = (gy + 1.f) / 2.f * (float)(P.H - 1);
+            const bool inr = fx > -1.f && fx < (float)P.W && fy > -1.f && fy < (float)P.H;
+            fx = fminf(fmaxf(fx, -2.f), (float)P.W + 1.f);
+            fy = fminf(fmaxf(fy, -2.f), (float)P.H + 1.f);
+            const float x0f = floorf(fx), y0f = floorf(fy);
+            const int x0 = (int)x0f, y0 = (int)y0f, x1 = x0 + 1, y1 = y0 + 1;
+            const float wx1 = fx - x0f, wx0 = (x0f + 1.f) - fx, wy1 = fy - y0f, wy0 = (y0f + 1.f) - fy;
+            const float go = dlogits[(size_t)b * P.capK + box] / 28.f;
+            const bool xin0 = x0 >= 0 && x0 < P.W, xin1 = x1 >= 0 && x1 < P.W;
+            const bool yin0 = y0 >= 0 && y0 < P.H, yin1 = y1 >= 0 && y1 < P.H;
+            const unsigned long long id = (unsigned long long)(i * 4);
+            if (inr) {
+                if (yin0 && xin0) { kk[0] = ((unsigned long long)((size_t)y0 * P.W + x0) << 32) | id; vv[0] = go * wx0 * wy0; }
+                if (yin0 && xin1) { kk[1] = ((unsigned long long)((size_t)y0 * P.W + x1) << 32) | (id + 1); vv[1] = go * wx1 * wy0; }
+                if (yin1 && xin0) { kk[2] = ((unsigned long long)((size_t)y1 * P.W + x0) << 32) | (id + 2); vv[2] = go * wx0 * wy1; }
+                if (yin1 && xin1) { kk[3] = ((unsigned long long)((size_t)y1 * P.W + x1) << 32) | (id + 3); vv[3] = go * wx1 * wy1; }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { key[i * 4 + q] = kk[q]; val[i * 4 + q] = vv[q]; }
+        }
+        for (int i = ne + threadIdx.x; i < P2; i += 256) key[i] = ~0ull;
+        __syncthreads();
+        for (int size = 2; size <= P2; size <<= 1) {
+            for (int stride = size >> 1; stride > 0; stride >>= 1) {
+                for (int i = threadIdx.x; i < P2 / 2; i += 256) {
+                    const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
+                    const bool asc = (lo & size) == 0;
+                    const unsigned long long a = key[lo], c = key[hi];
+                    if ((a > c) == asc) { key[lo] = c; key[hi] = a; }
+                }
+                __syncthreads();
+            }
+        }
+        {
+#pragma clang fp contract(off)
+            for (int i = threadIdx.x; i < P2; i += 256) {
+                const unsigned long long kk = key[i];
+                if (kk == ~0ull) continue;
+                const unsigned pix = (unsigned)(kk >> 32);
+                if (i > 0 && (unsigned)(key[i - 1] >> 32) == pix) continue;        // not the first tap of its pixel
+                float acc = di[pix];
+                for (int j = i; j < P2 && (unsigned)(key[j] >> 32) == pix; ++j) acc = acc + val[(unsigned)key[j]];
+                di[pix] = acc;
+            }
+        }
+        __threadfence();                       // this chunk's sums are visible to the next chunk's read-modify-write
+        __syncthreads();
     }
 }
 
@@ -597,8 +684,37 @@ extern "C" int sassd_pswarp_sample_bwd(const float *feat, int batch, int H, int 
     P.offx = grid_off_x; P.offy = grid_off_y; P.scale = spatial_scale;
     linspace_f32(-0.5f, 0.5f, 4, P.lin4);
     linspace_f32(-0.5f, 0.5f, 7, P.lin7);
-    hipLaunchKernelGGL(pswarp_bwd_kernel, dim3(cdiv(capK, 8), batch), dim3(256), 0, (hipStream_t)stream_, P, dlogits,
+    hipLaunchKernelGGL(pswarp_bwd_kernel<true>, dim3(cdiv(capK, 8), batch), dim3(256), 0, (hipStream_t)stream_, P, dlogits,
                        dfeat, dguided);
+    return sassd_launch_status();
+}
+
+extern "C" size_t sassd_pswarp_sample_bwd_det_workspace_bytes(int batch, int capK)
+{
+    (void)batch; (void)capK;
+    return 0;                                  // the taps are sorted in LDS, chunk by chunk: no device scratch
+}
+
+extern "C" int sassd_pswarp_sample_bwd_det(const float *feat, int batch, int H, int W, const float *guided,
+                                           const int32_t *counts, int capK, float grid_off_x, float grid_off_y,
+                                           float spatial_scale, const float *dlogits, float *dfeat, float *dguided,
+                                           void *ws, size_t ws_bytes, void *stream_)
+{
+    if (!feat || !guided || !counts || !dlogits || !dfeat || batch < 1 || capK < 1 || H < 1 || W < 1) return SASSD_EINVAL;
+    if ((long)H * W >= (1L << 32) - 1 || (long)batch * 28 >= (1L << 31)) return SASSD_EINVAL;
+    if (ws_bytes < sassd_pswarp_sample_bwd_det_workspace_bytes(batch, capK)) return SASSD_ENOSPC;
+    (void)ws;
+    WarpParams P;
+    P.feat = feat; P.guided = guided; P.counts = counts; P.logits = nullptr;
+    P.B = batch; P.H = H; P.W = W; P.capK = capK;
+    P.offx = grid_off_x; P.offy = grid_off_y; P.scale = spatial_scale;
+    linspace_f32(-0.5f, 0.5f, 4, P.lin4);
+    linspace_f32(-0.5f, 0.5f, 7, P.lin7);
+    hipStream_t s = (hipStream_t)stream_;
+    hipLaunchKernelGGL(pswarp_dfeat_det_kernel, dim3(batch * 28), dim3(256), 0, s, P, dlogits, dfeat);
+    if (dguided)
+        hipLaunchKernelGGL(pswarp_bwd_kernel<false>, dim3(cdiv(capK, 8), batch), dim3(256), 0, s, P, dlogits, dfeat,
+                           dguided);
     return sassd_launch_status();
 }
 

@@ -85,6 +85,64 @@ extern "C" int sassd_grad_sumsq(const float *grad, long n, float *out, void *str
     return sassd_launch_status();
 }
 
+// ---- deterministic mode: sassd_grad_sumsq_det ------------------------------------------------------------------------
+// Stage 1: sumsq_det_blocks(n) workgroups (a function of n only); thread t of block b sums the float4 chunks
+// i = b * 256 + t + k * (blocks * 256), k = 0, 1, .. in order (fp32, v.x*v.x + v.y*v.y + v.z*v.z + v.w*v.w left to
+// right), block 0's first n % 4 threads then add the tail element n4 * 4 + t; a fixed shuffle tree and the four wave sums
+// (w0 + w1) + (w2 + w3) give the block partial.  Stage 2: one workgroup sums the partials in double, thread t taking
+// partials t, t + 256, .. in order, then a fixed tree; the result is WRITTEN (rounded to fp32).
+namespace {
+int sumsq_det_blocks(long n) { return (int)std::min<long>(1024, std::max<long>(1, (n / 4 + 255) / 256)); }
+
+__global__ void __launch_bounds__(256) sumsq_det_part_kernel(const float *__restrict__ g, long n, float *__restrict__ part)
+{
+    float acc = 0.f;
+    const long n4 = n >> 2;
+    const f32x4 *g4 = reinterpret_cast<const f32x4 *>(g);
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const f32x4 v = g4[i];
+        acc += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const float v = g[(n4 << 2) + threadIdx.x];
+        acc += v * v;
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+    __shared__ float w[4];
+    if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = (w[0] + w[1]) + (w[2] + w[3]);
+}
+
+__global__ void __launch_bounds__(256) sumsq_det_final_kernel(const float *__restrict__ part, int nb, float *__restrict__ out)
+{
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < nb; i += 256) acc += (double)part[i];
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+    __shared__ double w[4];
+    if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) out[0] = (float)((w[0] + w[1]) + (w[2] + w[3]));
+}
+}  // namespace
+
+extern "C" size_t sassd_grad_sumsq_det_workspace_bytes(long n)
+{
+    if (n < 0) return 0;
+    return align_up((size_t)sumsq_det_blocks(n) * sizeof(float), 256);
+}
+
+extern "C" int sassd_grad_sumsq_det(const float *grad, long n, float *out, void *ws, size_t ws_bytes, void *stream_)
+{
+    if (!grad || !out || !ws || n < 0 || ((uintptr_t)grad & 15)) return SASSD_EINVAL;
+    if (ws_bytes < sassd_grad_sumsq_det_workspace_bytes(n)) return SASSD_ENOSPC;
+    hipStream_t s = (hipStream_t)stream_;
+    const int blocks = sumsq_det_blocks(n);
+    hipLaunchKernelGGL(sumsq_det_part_kernel, dim3(blocks), dim3(256), 0, s, grad, n, (float *)ws);
+    hipLaunchKernelGGL(sumsq_det_final_kernel, dim3(1), dim3(256), 0, s, (const float *)ws, blocks, out);
+    return sassd_launch_status();
+}
+
 extern "C" int sassd_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n,
                                const float *grad_sumsq, float lr, float beta1, float beta2, float eps,
                                float weight_decay, int step, float max_norm, float grad_scale, void *stream_)

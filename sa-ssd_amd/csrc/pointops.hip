@@ -4,6 +4,7 @@
 //   pts_in_boxes3d                         mmdet/ops/points_op/src/points_op.cpp:92-144 (a serial CPU loop after a
 //                                          .cpu() sync in the reference, cmn.py:48-54)
 #include "common.h"
+#include "inv_index.h"
 
 namespace {
 
@@ -369,5 +370,71 @@ extern "C" int sassd_pts_in_boxes3d(const float *pts, int n, const float *boxes3
     if (!pts || !boxes3d) return SASSD_EINVAL;
     hipLaunchKernelGGL(pts_in_boxes3d_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream_, pts, n, boxes3d,
                        m, pts_flag, reg_target);
+    return sassd_launch_status();
+}
+
+// ---- deterministic mode: sassd_three_interpolate_grad_det ------------------------------------------------------------
+namespace {
+// one thread per (row, channel): grad_points[r, ch] (value on entry) + fl(grad_out[p, ch] * weight[p, j]) over the row's
+// entries in ascending (p, j), one at a time, no contraction
+__global__ void __launch_bounds__(256) three_interpolate_gather_det_kernel(int c, const float *__restrict__ grad_out,
+                                                                           const float *__restrict__ weight,
+                                                                           float *__restrict__ grad_points, InvIndex X)
+{
+#pragma clang fp contract(off)
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long)X.rows * c) return;
+    const int r = (int)(t / c), ch = (int)(t - (long)r * c);
+    const int lo = X.start[r], hi = X.start[r + 1];
+    const int *__restrict__ lst = X.sorted;
+    float acc = grad_points[t];
+    int k = lo;
+    for (; k + 8 <= hi; k += 8) {
+        float pr[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int e = lst[k + q], p = e / 3;
+            pr[q] = grad_out[(size_t)p * c + ch] * weight[e];
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) acc = acc + pr[q];
+    }
+    for (; k < hi; ++k) {
+        const int e = lst[k], p = e / 3;
+        const float pr = grad_out[(size_t)p * c + ch] * weight[e];
+        acc = acc + pr;
+    }
+    grad_points[t] = acc;
+}
+
+bool tig_det_shape_ok(int c, int n, int m)
+{
+    return c >= 1 && n >= 0 && m >= 0 && (long)n * 3 < (1L << 31) - 1 && (long)m * c < (1L << 40);
+}
+}  // namespace
+
+extern "C" size_t sassd_three_interpolate_grad_det_workspace_bytes(int n, int m)
+{
+    if (n < 0 || m < 0 || (long)n * 3 >= (1L << 31) - 1) return 0;
+    return inv_index_bytes(1, n, m);
+}
+
+extern "C" int sassd_three_interpolate_grad_det(int c, int n, int m, const float *grad_out, const int32_t *idx,
+                                                const float *weight, float *grad_points, void *ws, size_t ws_bytes,
+                                                void *stream_)
+{
+    if (!tig_det_shape_ok(c, n, m) || !idx || !weight || !grad_points || !ws) return SASSD_EINVAL;
+    if (n > 0 && !grad_out) return SASSD_EINVAL;
+    if (ws_bytes < sassd_three_interpolate_grad_det_workspace_bytes(n, m)) return SASSD_ENOSPC;
+    if (n == 0 || m == 0) return SASSD_OK;                     // nothing lands: grad_points keeps its value
+    hipStream_t s = (hipStream_t)stream_;
+    InvIndex X = {};
+    X.levels = 1; X.n = n; X.rows = m;
+    X.idx[0] = idx; X.M[0] = m; X.row0[0] = 0;
+    inv_index_carve(X, ws);
+    inv_index_build(X, s);
+    const long tot = (long)m * c;
+    hipLaunchKernelGGL(three_interpolate_gather_det_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, c,
+                       grad_out, weight, grad_points, X);
     return sassd_launch_status();
 }

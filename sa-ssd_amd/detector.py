@@ -358,7 +358,7 @@ class SpMiddleFHD(nn.Module):
     # small torch / library launches; False keeps the module-by-module formulation (A/B, parity tests).
     fused_aux = True
 
-    def _aux_loss_fused(self, ctx, gt_bboxes):
+    def _aux_loss_fused(self, ctx, gt_bboxes, deterministic=False):
         """aux_loss on the fused kernels: `ctx` = (voxel_features, coors, middle tensors, batch size) left by forward."""
         voxel_features, coors, middle, batch_size = ctx
         dev = voxel_features.device
@@ -375,15 +375,17 @@ class SpMiddleFHD(nn.Module):
             nn_idx.append(idx)
             nn_d2.append(d2)
         sums = AuxHeadFn.apply(middle[0].features, middle[1].features, middle[2].features, self.point_fc.weight,
-                               self.point_cls.weight, self.point_reg.weight, nn_idx, nn_d2, label, target, npos)
+                               self.point_cls.weight, self.point_reg.weight, nn_idx, nn_d2, label, target, npos,
+                               bool(deterministic))
         n = len(gt_bboxes)
         cls_term, reg_term = _scaled_terms(sums, (1.0 / n, 1.0 / n))
         return dict(aux_loss_cls=cls_term, aux_loss_reg=reg_term)
 
-    def aux_loss(self, points, point_cls, point_reg, gt_bboxes):
-        """cmn.py:74-104."""
+    def aux_loss(self, points, point_cls, point_reg, gt_bboxes, deterministic=False):
+        """cmn.py:74-104.  deterministic: the fused backward sums in a fixed order (sassd_aux_head_bwd_det); the module
+        path's three_interpolate follows torch.use_deterministic_algorithms."""
         if point_cls is None and isinstance(points, tuple):      # forward() left the fused context
-            return self._aux_loss_fused(points, gt_bboxes)
+            return self._aux_loss_fused(points, gt_bboxes, deterministic)
         n = len(gt_bboxes)
         pts_labels, center_targets = self.build_aux_target(points, gt_bboxes)
         pos, neg = (pts_labels > 0).float(), (pts_labels == 0).float()
@@ -715,8 +717,9 @@ class PSWarpHead(nn.Module):
                                    nn.BatchNorm2d(oc, eps=1e-3, momentum=0.01), nn.ReLU(inplace=True),
                                    _HipConv2d(oc, oc, 1, 1, padding=0, bias=False))
 
-    def forward(self, x, guided_anchors, is_test=False):
-        """guided_anchors: list (per sample) of [K,7] device tensors -> list of [K] logits."""
+    def forward(self, x, guided_anchors, is_test=False, deterministic=False):
+        """guided_anchors: list (per sample) of [K,7] device tensors -> list of [K] logits.  deterministic: the backward
+        sums the feature gradient in ascending box order (sassd_pswarp_sample_bwd_det)."""
         grad = torch.is_grad_enabled() and (x.requires_grad or self.convs[0].weight.requires_grad)
         if self.training or grad:
             f = self._convs_train(x)
@@ -731,7 +734,7 @@ class PSWarpHead(nn.Module):
                 continue
             if grad:
                 scores.append(PSWarpFn.apply(f[i:i + 1], ga.float(), tuple(self.grid_offsets),
-                                             1.0 / self.featmap_stride))
+                                             1.0 / self.featmap_stride, bool(deterministic)))
                 continue
             cnt = torch.full((1,), k, dtype=torch.int32, device=x.device)
             lg = K.pswarp_sample(f[i:i + 1].contiguous(), ga.contiguous().view(1, k, 7), cnt, k, self.grid_offsets,
@@ -745,10 +748,10 @@ class PSWarpHead(nn.Module):
 
     fused_tail = True          # batched 3-D IoU + fused focal loss in loss_padded (False: the torch formulation, A/B)
 
-    def forward_padded(self, x, guided, counts):
+    def forward_padded(self, x, guided, counts, deterministic=False):
         """guided [B, capK, 7] padded, counts [B] int32 (device) -> logits [B, capK] (zero past a sample's count)."""
         return PSWarpBatchFn.apply(self._convs_train(x), guided.float(), counts, tuple(self.grid_offsets),
-                                   1.0 / self.featmap_stride)
+                                   1.0 / self.featmap_stride, bool(deterministic))
 
     def loss_padded(self, logits, gt_bboxes, guided, counts, cfg):
         """loss() on the padded batch: rotated 3-D IoU per sample (HIP overlap kernel), ONE sassd_assign_targets call for
@@ -914,15 +917,22 @@ class SingleStageDetector(nn.Module):
         self._plan_anchor_fp, self._plan_anchor_src = fp, anchors_src
         return self._plan
 
+    def deterministic_training(self):
+        """The deterministic training mode (include/sassd.h "Deterministic training"): the optional top-level
+        train_cfg['deterministic'] or torch.use_deterministic_algorithms(True)."""
+        cfg = self.train_cfg or {}
+        return bool(cfg.get('deterministic', False)) or torch.are_deterministic_algorithms_enabled()
+
     def forward_train(self, img, img_meta, **kwargs):
         """single_stage.py:75-108 -> dict of loss tensors."""
         batch_size = len(img_meta)
+        det = self.deterministic_training()
         ret = self.merge_second_batch(kwargs)
         vx = self.backbone(ret['voxels'], ret['num_points'])
         x, conv6, point_misc = self.neck(vx, ret['coordinates'], batch_size, is_test=False,
                                          indice_dict=ret.get('sassd_rulebooks'))
         losses = dict()
-        losses.update(self.neck.aux_loss(*point_misc, gt_bboxes=ret['gt_bboxes']))
+        losses.update(self.neck.aux_loss(*point_misc, gt_bboxes=ret['gt_bboxes'], deterministic=det))
         if not self.with_rpn:
             raise NotImplementedError
         rpn_outs = self.rpn_head(x)
@@ -937,13 +947,13 @@ class SingleStageDetector(nn.Module):
             guided, counts = self.rpn_head.get_guided_anchors_padded(
                 *rpn_outs, ret['anchors'], ret['anchors_mask'], ret['gt_bboxes'], thr=rpn_cfg.anchor_thr,
                 cap=rpn_cfg.get('guided_cap'))
-            score = extra.forward_padded(conv6, guided, counts)
+            score = extra.forward_padded(conv6, guided, counts, deterministic=det)
             losses.update(extra.loss_padded(score, ret['gt_bboxes'], guided, counts, self.train_cfg.extra))
             return losses
         guided, _ = self.rpn_head.get_guided_anchors(*rpn_outs, ret['anchors'], ret['anchors_mask'], ret['gt_bboxes'],
                                                      ret['gt_labels'], thr=rpn_cfg.anchor_thr)
         if extra is not None:
-            score = extra(conv6, guided)
+            score = extra(conv6, guided, deterministic=det)
             losses.update(extra.loss(score, ret['gt_bboxes'], ret['gt_labels'], guided, self.train_cfg.extra))
         return losses
 

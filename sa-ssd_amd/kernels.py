@@ -807,11 +807,21 @@ def pswarp_sample(feat, guided, counts, cap_k, grid_offsets, spatial_scale, logi
     return logits
 
 
-def pswarp_sample_bwd(feat, guided, counts, cap_k, grid_offsets, spatial_scale, dlogits):
-    """-> (dfeat [B,28,H,W], dguided [B,capK,7])."""
+def pswarp_sample_bwd(feat, guided, counts, cap_k, grid_offsets, spatial_scale, dlogits, deterministic=False):
+    """-> (dfeat [B,28,H,W], dguided [B,capK,7]).  deterministic: dfeat summed in ascending box order per pixel
+    (sassd_pswarp_sample_bwd_det) instead of float atomics."""
     b, parts, h, w = feat.shape
     dfeat = torch.zeros_like(feat)
     dg = torch.zeros(b, cap_k, 7, dtype=torch.float32, device=feat.device)
+    if deterministic:
+        L = _C.lib()
+        wsb = L.sassd_pswarp_sample_bwd_det_workspace_bytes(b, cap_k)
+        ws = workspace("pswarp_det", wsb, feat.device)
+        rc = L.sassd_pswarp_sample_bwd_det(_C.ptr(feat), b, h, w, _C.ptr(guided), _C.ptr(counts), cap_k,
+                                           float(grid_offsets[0]), float(grid_offsets[1]), float(spatial_scale),
+                                           _C.ptr(dlogits), _C.ptr(dfeat), _C.ptr(dg), _C.ptr(ws), wsb, _C.stream())
+        _C.check(rc, "sassd_pswarp_sample_bwd_det")
+        return dfeat, dg
     rc = _C.lib().sassd_pswarp_sample_bwd(_C.ptr(feat), b, h, w, _C.ptr(guided), _C.ptr(counts), cap_k,
                                           float(grid_offsets[0]), float(grid_offsets[1]), float(spatial_scale),
                                           _C.ptr(dlogits), _C.ptr(dfeat), _C.ptr(dg), _C.stream())
@@ -923,10 +933,19 @@ def three_interpolate(points, idx, weight):
     return out
 
 
-def three_interpolate_grad(grad_out, idx, weight, m):
-    _chk_cuda(grad_out, idx, weight)
+def three_interpolate_grad(grad_out, idx, weight, m, deterministic=False, grad_points=None):
+    """-> grad_points [m, C] (+)= the 3-NN interpolation gradient.  grad_points: the buffer to accumulate into (zeros
+    when None).  deterministic: ascending (point, neighbour) order per row (sassd_three_interpolate_grad_det)."""
+    _chk_cuda(grad_out, idx, weight, grad_points)
     n, c = grad_out.shape
-    gp = torch.zeros(m, c, dtype=torch.float32, device=grad_out.device)
+    gp = torch.zeros(m, c, dtype=torch.float32, device=grad_out.device) if grad_points is None else grad_points
+    if deterministic:
+        L = _C.lib()
+        wsb = L.sassd_three_interpolate_grad_det_workspace_bytes(n, m)
+        ws = workspace("three_interpolate_grad_det", wsb, grad_out.device)
+        _C.check(L.sassd_three_interpolate_grad_det(c, n, m, _C.ptr(grad_out), _C.ptr(idx), _C.ptr(weight), _C.ptr(gp),
+                                                    _C.ptr(ws), wsb, _C.stream()), "sassd_three_interpolate_grad_det")
+        return gp
     _C.check(_C.lib().sassd_three_interpolate_grad(c, n, m, _C.ptr(grad_out), _C.ptr(idx), _C.ptr(weight), _C.ptr(gp),
                                                    _C.stream()), "sassd_three_interpolate_grad")
     return gp
@@ -953,10 +972,18 @@ def mfma_probe(a32, b32, a16, b16, ksteps):
     return d32, d16
 
 
-def grad_sumsq(grad_flat, out=None):
-    """sum(grad^2) of a flat fp32 buffer -> device float [1] (no host sync)."""
+def grad_sumsq(grad_flat, out=None, deterministic=False):
+    """sum(grad^2) of a flat fp32 buffer -> device float [1] (no host sync).  deterministic: a summation order that
+    depends on the length only (sassd_grad_sumsq_det)."""
     _chk_cuda(grad_flat)
     out = torch.empty(1, dtype=torch.float32, device=grad_flat.device) if out is None else out
+    if deterministic:
+        L = _C.lib()
+        wsb = L.sassd_grad_sumsq_det_workspace_bytes(grad_flat.numel())
+        ws = workspace("grad_sumsq_det", wsb, grad_flat.device)
+        _C.check(L.sassd_grad_sumsq_det(_C.ptr(grad_flat), grad_flat.numel(), _C.ptr(out), _C.ptr(ws), wsb, _C.stream()),
+                 "sassd_grad_sumsq_det")
+        return out
     _C.check(_C.lib().sassd_grad_sumsq(_C.ptr(grad_flat), grad_flat.numel(), _C.ptr(out), _C.stream()),
              "sassd_grad_sumsq")
     return out
@@ -1208,8 +1235,9 @@ def aux_head_fwd(feats, nn_idx, nn_d2, w1, w2, label, target, npos):
     return sums, wgt, h, out, gout
 
 
-def aux_head_bwd(feats, nn_idx, w1, w2, wgt, h, gout, grad_sums):
-    """-> (grad_feats [3 x [M_s, C_s]], dw1 [64,160], dw2 [4,64])."""
+def aux_head_bwd(feats, nn_idx, w1, w2, wgt, h, gout, grad_sums, deterministic=False):
+    """-> (grad_feats [3 x [M_s, C_s]], dw1 [64,160], dw2 [4,64]).  deterministic: the feature gradients summed in
+    ascending (point, neighbour) order per voxel row (sassd_aux_head_bwd_det)."""
     import ctypes as C
     _chk_cuda(w1, w2, wgt, h, gout, grad_sums, *feats, *nn_idx)
     n = h.shape[0]
@@ -1219,6 +1247,13 @@ def aux_head_bwd(feats, nn_idx, w1, w2, wgt, h, gout, grad_sums):
     dw2 = torch.empty(4, 64, dtype=torch.float32, device=dev)
     m = (C.c_int * 3)(*[int(f.shape[0]) for f in feats])
     L = _C.lib()
+    if deterministic:
+        wsb = L.sassd_aux_head_bwd_det_workspace_bytes(n, m)
+        ws = workspace("aux_head_det", wsb, dev)
+        _C.check(L.sassd_aux_head_bwd_det(n, _ptr3(feats), m, _ptr3(nn_idx), _C.ptr(w1), _C.ptr(w2), _C.ptr(wgt),
+                                          _C.ptr(h), _C.ptr(gout), _C.ptr(grad_sums), _ptr3(gf), _C.ptr(dw1), _C.ptr(dw2),
+                                          _C.ptr(ws), wsb, _C.stream()), "sassd_aux_head_bwd_det")
+        return gf, dw1, dw2
     wsb = L.sassd_aux_head_workspace_bytes(n)
     ws = workspace("aux_head", wsb, dev)
     _C.check(L.sassd_aux_head_bwd(n, _ptr3(feats), m, _ptr3(nn_idx), _C.ptr(w1), _C.ptr(w2), _C.ptr(wgt), _C.ptr(h),

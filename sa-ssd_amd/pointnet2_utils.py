@@ -47,7 +47,9 @@ class ThreeInterpolate(Function):
     @staticmethod
     def backward(ctx, grad_out):
         idx, weight, m = ctx.three_interpolate_for_backward
-        return K.three_interpolate_grad(grad_out.contiguous().float(), idx, weight.contiguous().float(), m), None, None
+        # torch.use_deterministic_algorithms(True): ascending (point, neighbour) order instead of float atomics
+        return K.three_interpolate_grad(grad_out.contiguous().float(), idx, weight.contiguous().float(), m,
+                                        deterministic=torch.are_deterministic_algorithms_enabled()), None, None
 
 
 three_interpolate = ThreeInterpolate.apply

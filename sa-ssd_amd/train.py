@@ -249,13 +249,14 @@ class CosineWarmupLR:
 
 
 class AdamOneCycle:
-    def __init__(self, model, lr, weight_decay, beta2=0.99, eps=1e-8, grad_clip=None, world_size=1):
+    def __init__(self, model, lr, weight_decay, beta2=0.99, eps=1e-8, grad_clip=None, world_size=1, deterministic=False):
         self.flat = model if isinstance(model, FlatParams) else FlatParams(model)
         self.lr, self.mom, self.wd, self.beta2, self.eps = lr, 0.9, weight_decay, beta2, eps
         self.max_norm = float(grad_clip["max_norm"]) if grad_clip else 0.0
         if grad_clip and grad_clip.get("norm_type", 2) != 2:
             raise NotImplementedError("only the L2 gradient-norm clip of the reference configs")
         self.world_size = world_size
+        self.deterministic = bool(deterministic)   # the clip's square sum in a length-only order (sassd_grad_sumsq_det)
         self.exp_avg = torch.zeros_like(self.flat.data)
         self.exp_avg_sq = torch.zeros_like(self.flat.data)
         self.sumsq = torch.zeros(1, dtype=torch.float32, device=self.flat.data.device)
@@ -268,7 +269,7 @@ class AdamOneCycle:
     def step(self):
         self.steps += 1
         grad = self.flat.grad                                 # gathers this step's gradients (one multi-tensor copy)
-        sumsq = K.grad_sumsq(grad, self.sumsq) if self.max_norm > 0 else None
+        sumsq = K.grad_sumsq(grad, self.sumsq, deterministic=self.deterministic) if self.max_norm > 0 else None
         K.adam_step(self.flat.data, grad, self.exp_avg, self.exp_avg_sq, sumsq, self.lr, self.mom,
                     self.beta2, self.eps, self.wd, self.steps, self.max_norm, 1.0 / self.world_size)
         K.bump_weights_generation()          # raw-pointer update: parameter `_version`s did not move
@@ -286,11 +287,20 @@ class AdamOneCycle:
         K.bump_weights_generation()
 
 
-def build_optimizer(model, optim_cfg, world_size=1):
+def resolve_deterministic(model, deterministic=None):
+    """The deterministic training mode: an explicit True / False wins; None -> the model's optional top-level
+    train_cfg['deterministic'] or torch.use_deterministic_algorithms(True)."""
+    if deterministic is not None:
+        return bool(deterministic)
+    cfg = getattr(model, "train_cfg", None) or {}
+    return bool(cfg.get("deterministic", False)) or torch.are_deterministic_algorithms_enabled()
+
+
+def build_optimizer(model, optim_cfg, world_size=1, deterministic=None):
     if optim_cfg["type"] != "adam_onecycle":
         raise NotImplementedError("the SA-SSD configs train with 'adam_onecycle'")
     opt = AdamOneCycle(model, optim_cfg["lr"], optim_cfg["weight_decay"], grad_clip=optim_cfg.get("grad_clip"),
-                       world_size=world_size)
+                       world_size=world_size, deterministic=resolve_deterministic(model, deterministic))
     if opt.flat.data.is_cuda and optim_cfg.get("pack_plan", True):
         opt.pack_plan = PackPlan(model, opt.flat)
         opt.flat.pack_plan = opt.pack_plan        # GradSync re-runs it after the parameter broadcast
