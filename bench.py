@@ -4,6 +4,11 @@
   python bench.py --gpus N --steps K --warmup W      N > 1 without a torchrun environment: bench.py re-executes itself
                                                      under torch.distributed.run with N ranks (one per GPU, RCCL)
   python bench.py ... --dump-outputs DIR              also write what the last timed step computed as DIR/<name>.npy
+  python bench.py ... --full                          also measure everything else the line can carry (below)
+
+A plain run does only what its headline figure needs: set-up, W warm-up steps, the K timed steps, --dump-outputs, and the JSON
+line (metric, value, unit, ms_per_step, dtype, ... of the timed steps).  Every other record -- the sequential and host-synced
+rates, per-stage timings, rooflines, the training half, the other configs, the CPU baseline -- is taken only with --full.
 
 A "step" = one whole pass of the hot path over one batch of synthetic frames, raw points resident in HBM ->
 voxelize -> 7 rulebooks -> 14 sparse convs -> densify -> BEVNet -> heads -> anchors mask -> decode/filter -> PSWarp
@@ -16,17 +21,18 @@ across ranks with no data-path collective (weak scaling); value = frames of all 
   --mode train    the training record alone: configs[2] (car_cfg, batch 2 per GPU, bf16, DDP); with --config waymo
                   configs[4] (180k-point frames, 0.1 m voxels, batch 4 per GPU)
 
-The default run (car) measures BOTH halves of BASELINE.json's metric: after the inference timing every rank runs the
+With --full the car run measures BOTH halves of BASELINE.json's metric: after the inference timing every rank runs the
 configs[2] training step (--train-steps / --train-warmup) and the record -- samples/s, ms per step (max over ranks and
 per rank), all-reduce time, the six loss terms, the roofline of the dominant training kernel -- rides in the same JSON
-line as `train` (--no-train skips it).
+line as `train` (--no-train skips it); configs[3] / [4] follow as `infer_multi`, `infer_waymo`, `train_waymo` (--no-extra
+skips them).  `--mode train` alone carries the roofline of its dominant kernel with --full only.
 
 By default three frames are in flight per GPU (--inflight): independent plans / graphs on separate HIP streams, so one
 frame's latency-bound sparse / post stages overlap another frame's MFMA-bound BEV stage; each frame is still a batch-1
-pass.  `fps_sequential` (one graph after the other on one stream, no host sync) and `latency_ms_sync_per_frame` (host
-sync + result read-back per frame) are printed next to it.
+pass.  With --full, `fps_sequential` (one graph after the other on one stream, no host sync) and
+`latency_ms_sync_per_frame` (host sync + result read-back per frame) are printed next to it.
 
-The JSON line also carries:
+With --full the JSON line also carries:
   roofline         dominant kernel (the 36-GEMM launch of a BEV 3x3 layer, Winograd F(4x4,3x3); fp32 products computed as
                    8 bf16 piece products each on the bf16 MFMA over exactly-split operands):
                    `achieved` / `frac` = the flops the kernel EXECUTES on the MFMA pipe (1/4 of the direct convolution,
@@ -208,24 +214,27 @@ def stamped_traffic(fname):
 
 
 def train_measure(args, dev, rank, world, config="car", precision="bf16", steps=40, warmup=8, batch=0, frames=16,
-                  fused_bn=None, dump_dir=None):
+                  fused_bn=None, dump_dir=None, roofline=True):
     """_train_measure with the process-wide training switches (BEV precision, fused sparse BatchNorm) restored afterwards,
     whatever happens inside: the inference half of the default line runs in the same process."""
     from sassd import autograd as AG, spconv as SP
     prev = (AG.bev_precision(), SP.SparseSequential.fuse_bn_relu)
     try:
-        return _train_measure(args, dev, rank, world, config, precision, steps, warmup, batch, frames, fused_bn, dump_dir)
+        return _train_measure(args, dev, rank, world, config, precision, steps, warmup, batch, frames, fused_bn, dump_dir,
+                              roofline)
     finally:
         AG.set_bev_precision(prev[0])
         SP.SparseSequential.fuse_bn_relu = prev[1]
 
 
-def _train_measure(args, dev, rank, world, config, precision, steps, warmup, batch, frames, fused_bn, dump_dir=None):
+def _train_measure(args, dev, rank, world, config, precision, steps, warmup, batch, frames, fused_bn, dump_dir=None,
+                   roofline=True):
     """The training half of the BASELINE metric.  config "car": BASELINE configs[2] (car_cfg training, batch 2 / GPU,
     bf16 MFMA operands in the BEV convs); "waymo": configs[4] (180k-point frames, 0.1 m voxels, batch 4 / GPU).
     A step = device voxelize + anchor masks + rulebooks (side stream) + forward_train + backward + bucketed gradient
     all-reduce (RCCL) + fused clip / AdamW update + one-launch weight re-pack.  Returns the `train` record
-    (rank 0; None on the other ranks).  Reference loop: tools/train_utils/__init__.py:36-61, DDP wrap tools/train.py:78."""
+    (rank 0; None on the other ranks).  `roofline`: also time the dominant training kernel on its own (the record's
+    `roofline`).  Reference loop: tools/train_utils/__init__.py:36-61, DDP wrap tools/train.py:78."""
     from sassd import dist as D, train, autograd as AG
     AG.set_bev_precision(precision)
     if fused_bn is not None:
@@ -289,44 +298,46 @@ def _train_measure(args, dev, rank, world, config, precision, steps, warmup, bat
                                     **{"term_" + k: np.array(float(v), np.float64) for k, v in terms.items()}))
     per_rank = D.allgather_float(dt_local / steps * 1e3, dev) if world > 1 else [dt_local / steps * 1e3]
     voxels = int(sum(v.shape[0] for v in state["batch"]["voxels"]))
-    # dominant kernel of the training step, timed live with events on the launch stream: the 3x3 BEV conv (14 launches
-    # per step, forward + data gradient) -- bf16 direct kernel where the shape allows, else the fp32 Winograd F(4x4) layer
     from sassd import kernels as K
     H, W = model.neck.sparse_shape[1] // 8, model.neck.sparse_shape[2] // 8
-    xb = torch.randn(B, 256, H, W, device=dev)
-    wb = torch.randn(256, 256, 3, 3, device=dev) / 48
-    flops = 2.0 * B * H * W * 256 * 256 * 9
     bf16_conv = precision == "bf16" and K.conv2d_bf16_supported(256, 256, H, W)
-    if bf16_conv:
-        pk = K.conv2d_bf16_pack_weight(wb)
-        run, kname, peak = (lambda: K.conv2d_bf16_fwd(xb, pk, 256)), "conv2d_bf16_kernel (v_mfma_f32_32x32x16_bf16)", 2500.0
-    else:
-        pk = K.conv2d_wino4_pack_weight(wb)
-        run = lambda: K.conv2d_wino4_fwd(xb, pk, 256, None, None)       # noqa: E731
-        kname, peak = "wino4_in + wino4_gemm + wino4_out (fp32 MFMA, Winograd F(4x4): executed flops = direct / 4)", 157.3
-        flops /= 4.0
-    for _ in range(3):
-        run()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(20):
-        run()
-    e1.record()
-    torch.cuda.synchronize()
-    kms = e0.elapsed_time(e1) / 20
-    del xb, wb
+    roof = None
+    if roofline:
+        # dominant kernel of the training step, timed live with events on the launch stream: the 3x3 BEV conv (14 launches
+        # per step, forward + data gradient) -- bf16 direct kernel where the shape allows, else the fp32 Winograd F(4x4) layer
+        xb = torch.randn(B, 256, H, W, device=dev)
+        wb = torch.randn(256, 256, 3, 3, device=dev) / 48
+        flops = 2.0 * B * H * W * 256 * 256 * 9
+        if bf16_conv:
+            pk = K.conv2d_bf16_pack_weight(wb)
+            run, kname, peak = (lambda: K.conv2d_bf16_fwd(xb, pk, 256)), "conv2d_bf16_kernel (v_mfma_f32_32x32x16_bf16)", 2500.0
+        else:
+            pk = K.conv2d_wino4_pack_weight(wb)
+            run = lambda: K.conv2d_wino4_fwd(xb, pk, 256, None, None)       # noqa: E731
+            kname, peak = "wino4_in + wino4_gemm + wino4_out (fp32 MFMA, Winograd F(4x4): executed flops = direct / 4)", 157.3
+            flops /= 4.0
+        for _ in range(3):
+            run()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(20):
+            run()
+        e1.record()
+        torch.cuda.synchronize()
+        kms = e0.elapsed_time(e1) / 20
+        del xb, wb
+        traffic, at = (None, None)
+        if bf16_conv and B == 2 and config == "car":
+            rec, at = stamped_traffic(PROFILE_TAG + "_bf16_conv_hbm_traffic.json")
+            traffic = rec["traffic_bytes_per_launch"] if rec else None
+        roof = dict(bound="mfma", kernel=kname, achieved=round(flops / kms / 1e9, 1), peak=peak, unit="TFLOP/s",
+                    frac=round(flops / kms / 1e9 / peak, 4), ms_per_launch=round(kms, 4), traffic=traffic,
+                    traffic_measured_at=at,
+                    note="flops executed by one 256->256 3x3 BEV layer at batch %d (%dx%d map) / mean layer time (HIP events, "
+                         "20 launches on the launch stream); 14 such layers per step (forward + data gradient)" % (B, H, W))
     if rank != 0:
         return None
     sps = steps * B * world / dt
-    traffic, at = (None, None)
-    if bf16_conv and B == 2 and config == "car":
-        rec, at = stamped_traffic(PROFILE_TAG + "_bf16_conv_hbm_traffic.json")
-        traffic = rec["traffic_bytes_per_launch"] if rec else None
-    roof = dict(bound="mfma", kernel=kname, achieved=round(flops / kms / 1e9, 1), peak=peak, unit="TFLOP/s",
-                frac=round(flops / kms / 1e9 / peak, 4), ms_per_launch=round(kms, 4), traffic=traffic,
-                traffic_measured_at=at,
-                note="flops executed by one 256->256 3x3 BEV layer at batch %d (%dx%d map) / mean layer time (HIP events, 20 "
-                     "launches on the launch stream); 14 such layers per step (forward + data gradient)" % (B, H, W))
     bev = ("bf16 MFMA operands in the dense convs (BEV 3x3 + 1x1 and the head convs: fwd/dgrad/wgrad; fp32 accumulation, master weights and activations), "
            "fp32 sparse trunk" if bf16_conv else
            "bf16 weight gradients, fp32 Winograd forward / data gradient (the bf16 direct conv needs W %% 16 == 0, the "
@@ -349,7 +360,7 @@ def _train_measure(args, dev, rank, world, config, precision, steps, warmup, bat
         "config": {"workload": desc, "global_batch": B * world,
                    "parallelism": "ddp x%d (flat-gradient RCCL all-reduce in 4 buckets / step%s)" %
                                   (world, "; one-rank communicator forced" if (sync.on and world == 1) else "")},
-        "roofline": roof,
+        **({"roofline": roof} if roof is not None else {}),
         "final_loss": round(float(loss), 4), "loss_terms": {k: round(float(v), 4) for k, v in terms.items()},
         "final_loss_note": "after %d steps of a one-cycle schedule laid out for %d (5 x steps + warm-up): a sanity value "
                            "(finite, six non-zero terms), not comparable across --steps or with rounds 1-3, whose schedule "
@@ -367,7 +378,7 @@ def main_train(args):
         K0.DEFAULT_CFG["spconv"] = K0.spconv_cfg(args.spconv_cfg)     # host-side default of the binding, passed per call
     out = train_measure(args, dev, rank, world, "waymo" if args.config == "waymo" else "car", args.precision,
                         args.steps, args.warmup, args.batch if args.batch > 1 else 0, args.frames,
-                        False if args.torch_bn else None, dump_dir=args.dump_outputs)
+                        False if args.torch_bn else None, dump_dir=args.dump_outputs, roofline=args.full)
     if rank == 0:
         print(json.dumps(out))
 
@@ -500,10 +511,14 @@ def main():
                     "stream), so that `train.allreduce_ms` is measured on a single-GPU box")
     ap.add_argument("--steps", type=int, default=200, help="timed steps (exactly this many; ms_per_step = their time / steps)")
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="default (car) run: skip the `train` record (BASELINE "
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure every other record of the line: "
+                    "fps_sequential, latency, stage_ms, the rooflines, and for the car headline the `train`, `infer_multi`, "
+                    "`infer_waymo`, `train_waymo` and `cpu_baseline` records; --mode train: the training kernel's roofline.  "
+                    "Without it the run is set-up, warm-up, the timed steps, --dump-outputs and the headline line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full (car): skip the `cpu_baseline` record")
+    ap.add_argument("--no-train", action="store_true", help="--full (car): skip the `train` record (BASELINE "
                     "configs[2], the training half of the metric) that follows the inference measurement")
-    ap.add_argument("--train-steps", type=int, default=40, help="timed training steps of the default run's `train` record")
+    ap.add_argument("--train-steps", type=int, default=40, help="timed training steps of the `train` record (--full)")
     ap.add_argument("--train-warmup", type=int, default=8)
     ap.add_argument("--frames", type=int, default=16, help="distinct synthetic frames cycled through")
     ap.add_argument("--inflight", type=int, default=3, help="frames in flight: independent plans on separate HIP "
@@ -530,7 +545,7 @@ def main():
     ap.add_argument("--side-stream", action="store_true", help="the plans in flight keep their coordinate side stream: every frame "
                     "graph has two branches (the form of rounds 2-6; A/B).  Default: ONE branch per frame in flight -- "
                     "rulebooks / anchor masks in front of the feature path on the frame's own stream")
-    ap.add_argument("--no-extra", action="store_true", help="default (car) run: skip the `infer_multi` / `infer_waymo` / "
+    ap.add_argument("--no-extra", action="store_true", help="--full (car): skip the `infer_multi` / `infer_waymo` / "
                     "`train_waymo` records (BASELINE configs[3] / [4]) that follow the headline measurement")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last one "
                     "returned to its caller as DIR/<name>.npy: inference -- the detections of every frame of the step on "
@@ -625,8 +640,38 @@ def main():
     ndet = int(plan.det["counts"].sum().item())
     ncand = int(plan.df["counts"].sum().item())
     fps = args.steps * B * world / dt
+    headline = args.config == "car" and B == 1
+    frame_graph = "two branches (coordinate side stream)"
+    if one_branch:
+        frame_graph = ("one branch per frame in flight (rulebooks / anchor masks in front of the feature path on the frame's "
+                       "own stream)" + ("; fps_sequential, latency, per-stage timings and roofline_sparse on a two-branch plan "
+                                        "(one frame at a time: its coordinate work beside its first convolutions)"
+                                        if args.full else ""))
+    out = {
+        "metric": "KITTI-Car inference frames/sec (whole job)" if args.config == "car" else
+                  "%s inference frames/sec (whole job)" % args.config,
+        "value": round(fps, 3), "unit": "frames/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": round(fps / world / PUBLISHED_FPS, 3) if headline else None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "%s, batch=%d, random-init SA-SSD weights, points resident in HBM" % (w["desc"], B),
+                   "frames_per_step_per_gpu": B, "frames_in_flight": S, "spconv_cfg": args.spconv_cfg,
+                   "rulebook_pyramid": args.pyramid,
+                   "launch": "eager host launches" if args.eager else "one hipGraph replay per frame",
+                   "frame_graph": frame_graph,
+                   "hip_runtime_env": {"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES")},
+                   "parallelism": "frame-sharded x%d, no collective" % world,
+                   "vs_baseline_ref": "reference readme.md:2 '25 FPS' (hardware unstated), per-GPU fps / 25"},
+        "fps_in_flight": round(fps, 3),
+        "detections_last_frame": ndet, "guided_anchor_candidates_last_frame": ncand,
+        "csrc_hash": csrc_hash(),
+    }
+    if not args.full:                                    # the headline is complete: nothing else is measured
+        if rank == 0:
+            print(json.dumps(out))
+        return
 
-    # ---- everything below is measurement detail on top of the timed region -----------------------------------
+    # ---- everything below is measurement detail on top of the timed region (--full) ----------------------------
     # sequential: one graph after the other on ONE stream, no host sync in between
     # ONE frame at a time is the other deployment: there the frame's own coordinate work should overlap its first convolutions, i.e.
     # the two-branch graph (2 % faster sequentially than the one-branch graph the frames in flight use) -- these two numbers and
@@ -714,7 +759,6 @@ def main():
                 None, prev, wp, 256, cout, cm, B, H_, W_, scale, shift, True, iso_plan.act[1], ws, cfg=c))
             w4_parts["in"] = timed_part(32, lambda c: K.conv2d_wino4_chain(
                 iso_plan.dense, None, wp0, iso_plan.bev_cin[0], cout, cm, B, H_, W_, scale, shift, True, None, ws, cfg=c))
-    headline = args.config == "car" and B == 1
     # ---- the training half of BASELINE.json's metric (configs[2]: car_cfg, batch 2 / GPU, bf16, DDP): every rank takes
     # part (gradient all-reduce over RCCL at N > 1); the record rides in the same JSON line as `train` ------------------
     emit = {}
@@ -774,25 +818,8 @@ def main():
     if st:
         sp_counters = {k: dict(v["fraction_of_wave_cycles"], mfma_busy_fraction=v.get("mfma_busy_fraction"))
                        for k, v in st["kernels"].items() if k.startswith("spconv") and k.endswith("@" + args.config)} or None
-    out = {
-        "metric": "KITTI-Car inference frames/sec (whole job)" if args.config == "car" else
-                  "%s inference frames/sec (whole job)" % args.config,
-        "value": round(fps, 3), "unit": "frames/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
-        "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": round(fps / world / PUBLISHED_FPS, 3) if headline else None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "%s, batch=%d, random-init SA-SSD weights, points resident in HBM" % (w["desc"], B),
-                   "frames_per_step_per_gpu": B, "frames_in_flight": S, "spconv_cfg": args.spconv_cfg,
-                   "rulebook_pyramid": args.pyramid,
-                   "launch": "eager host launches" if args.eager else "one hipGraph replay per frame",
-                   "frame_graph": ("one branch per frame in flight (rulebooks / anchor masks in front of the feature path on the "
-                                   "frame's own stream); fps_sequential, latency, per-stage timings and roofline_sparse on a "
-                                   "two-branch plan (one frame at a time: its coordinate work beside its first convolutions)"
-                                   if one_branch else "two branches (coordinate side stream)"),
-                   "hip_runtime_env": {"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES")},
-                   "parallelism": "frame-sharded x%d, no collective" % world,
-                   "vs_baseline_ref": "reference readme.md:2 '25 FPS' (hardware unstated), per-GPU fps / 25"},
-        "fps_in_flight": round(fps, 3), "fps_sequential": round(B * 1e3 / seq_ms, 3),
+    out.update({
+        "fps_sequential": round(B * 1e3 / seq_ms, 3),
         "latency_ms_sync_per_frame": round(lat_ms, 3), "frame_graph_ms": None if frame_ms is None else round(frame_ms, 4),
         "roofline": {"bound": "mfma", "kernel": kname,
                      "achieved": round(exec_tf * mfma_mult, 2), "peak": mfma_peak, "unit": "TFLOP/s",
@@ -838,9 +865,7 @@ def main():
                                     "rate (see traffic)"},
         "stage_ms": {k: round(v, 4) for k, v in sorted(iso_ms.items())},
         "bev_total_ms": round(bev_total_ms, 4),
-        "detections_last_frame": ndet, "guided_anchor_candidates_last_frame": ncand,
-    }
-    out["csrc_hash"] = csrc_hash()
+    })
     # the inference measurement is complete: its plans, graphs and streams go before the other records of the line are taken (the
     # training record ran 238 instead of 276 samples/s with three captured frame graphs still alive in the process)
     del plans, plan                                        # (iso_plan stays: the parity record of cpu_baseline reads it)
@@ -852,7 +877,7 @@ def main():
             if world == 1:                                       # (N > 1: a collective -- every rank measures in this process)
                 try:
                     out["train"] = child_record(["--mode", "train", "--steps", str(args.train_steps), "--warmup",
-                                                 str(args.train_warmup)], 400)
+                                                 str(args.train_warmup), "--full"], 400)
                 except Exception as e:                           # fall back to the in-process measurement
                     out["train"] = train_measure(args, dev, rank, world, "car", "bf16", args.train_steps, args.train_warmup)
                     out["train"]["child_error"] = "%s: %s" % (type(e).__name__, e)
@@ -864,15 +889,16 @@ def main():
             watchdog.cancel()
     # ---- BASELINE configs[3] / [4] in the same line (N = 1 only: no collective, rank 0): short runs of the same measurement
     if world == 1 and headline and not args.no_extra and not args.eager:
-        pyr = ["--pyramid", args.pyramid]
+        common = ["--pyramid", args.pyramid, "--full"]   # (--full: the records keep fps_sequential, latency, roofline_sparse)
         keep = ("metric", "value", "unit", "ms_per_step", "steps", "warmup", "trials", "config", "fps_sequential",
                 "latency_ms_sync_per_frame", "roofline_sparse", "measured_by")
         for key, argv, fallback in (
-                ("infer_multi", ["--config", "multi", "--steps", "60", "--warmup", "10", "--no-cpu-baseline", "--inflight", str(S)] + pyr,
+                ("infer_multi", ["--config", "multi", "--steps", "60", "--warmup", "10", "--no-cpu-baseline", "--inflight", str(S)] + common,
                  lambda: infer_extra(dev, "multi", 60, 10, S, args.pyramid == "persistent")),
-                ("infer_waymo", ["--config", "waymo", "--steps", "40", "--warmup", "8", "--no-cpu-baseline", "--inflight", str(S)] + pyr,
+                ("infer_waymo", ["--config", "waymo", "--steps", "40", "--warmup", "8", "--no-cpu-baseline", "--inflight", str(S)] + common,
                  lambda: infer_extra(dev, "waymo", 40, 8, S, args.pyramid == "persistent")),
-                ("train_waymo", ["--mode", "train", "--config", "waymo", "--steps", "12", "--warmup", "4", "--frames", "8"],
+                ("train_waymo", ["--mode", "train", "--config", "waymo", "--steps", "12", "--warmup", "4", "--frames", "8",
+                                 "--full"],
                  lambda: train_measure(args, dev, rank, world, "waymo", "bf16", 12, 4, frames=8))):
             t0 = time.perf_counter()
             try:

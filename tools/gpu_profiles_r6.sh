@@ -41,16 +41,16 @@ pmc stall_sparse_car "$SQ" python $R/tools/run_sparse_only.py --config car --rep
 pmc stall_sparse_multi "$SQ" python $R/tools/run_sparse_only.py --config multi --reps 3
 pmc stall_wino4 "$SQ" python $R/tools/run_wino4.py --profile --reps 5
 python tools/collect_profiles.py r06 > $O/collect.log 2>&1; echo "collect rc=$?"
-timeout 900 python bench.py > $O/bench_default.log 2>&1; echo "bench default rc=$?"
+timeout 900 python bench.py --full > $O/bench_default.log 2>&1; echo "bench default rc=$?"
 ( time timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_20steps.log 2>&1 ) 2>&1 | grep real; echo "bench 20 steps (the driver's form) rc=$?"
-trace bench_inflight3 python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-train --no-extra
-trace bench_train python $R/bench.py --mode train --steps 10 --warmup 4
-timeout 600 python bench.py --mode train --steps 40 --warmup 8 > $O/bench_train_bf16.log 2>&1; echo "train bf16 rc=$?"
-timeout 600 python bench.py --mode train --steps 40 --warmup 8 --force-ddp > $O/bench_train_forceddp.log 2>&1; echo "train force-ddp rc=$?"
-timeout 600 python bench.py --mode train --precision fp32 --steps 30 --warmup 6 > $O/bench_train_fp32.log 2>&1; echo "train fp32 rc=$?"
-timeout 600 python bench.py --mode train --config waymo --steps 12 --warmup 4 > $O/bench_train_waymo.log 2>&1; echo "train waymo rc=$?"
-timeout 300 python bench.py --config multi --steps 30 --warmup 5 --no-cpu-baseline > $O/bench_multi.log 2>&1; echo "multi rc=$?"
-timeout 300 python bench.py --config waymo --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_waymo.log 2>&1; echo "waymo rc=$?"
+trace bench_inflight3 python $R/bench.py --steps 100 --warmup 10 --full --no-cpu-baseline --no-train --no-extra
+trace bench_train python $R/bench.py --mode train --steps 10 --warmup 4 --full
+timeout 600 python bench.py --mode train --steps 40 --warmup 8 --full > $O/bench_train_bf16.log 2>&1; echo "train bf16 rc=$?"
+timeout 600 python bench.py --mode train --steps 40 --warmup 8 --full --force-ddp > $O/bench_train_forceddp.log 2>&1; echo "train force-ddp rc=$?"
+timeout 600 python bench.py --mode train --precision fp32 --steps 30 --warmup 6 --full > $O/bench_train_fp32.log 2>&1; echo "train fp32 rc=$?"
+timeout 600 python bench.py --mode train --config waymo --steps 12 --warmup 4 --full > $O/bench_train_waymo.log 2>&1; echo "train waymo rc=$?"
+timeout 300 python bench.py --config multi --steps 30 --warmup 5 --full --no-cpu-baseline > $O/bench_multi.log 2>&1; echo "multi rc=$?"
+timeout 300 python bench.py --config waymo --steps 20 --warmup 5 --full --no-cpu-baseline > $O/bench_waymo.log 2>&1; echo "waymo rc=$?"
 timeout 300 python tools/run_bf16_conv.py --ablate > $O/bf16_conv_timing.json 2>/dev/null; echo "bf16 timing rc=$?"
 timeout 200 python tools/run_conv1x1_bf16.py 30 2>/dev/null | grep "^1x1" > $O/conv1x1_bf16_timing.txt; echo "bf16 1x1 timing rc=$?"
 timeout 400 python tools/ablate_spconv.py --config car --ablate 2>&1 | grep -v "^/opt" > $O/spconv_layers_car.txt; echo "layers car rc=$?"
