@@ -194,6 +194,40 @@ int sassd_densify_bf16(const float *feats, const int32_t *indices, const int32_t
                        int batch_size, int channel_order, void *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * bf16 sparse backbone (inference only: InferencePlan(sparse_precision="bf16"), test_cfg['sparse_precision']).  Chosen per plan
+ * and per call -- no process-wide switch; training stays fp32.  Arithmetic contract:
+ *   first layer (Cin = 4, the voxel means in metres: a bf16 ulp at 70 m is 0.5 m against a 0.05 m voxel)  x fp32 and the fp32
+ *            weights, fp32 accumulation, relu(acc * scale + shift) in fp32, the result stored rounded to bf16 (nearest even);
+ *   every other layer (submanifold, strided, the 1x1x1 `extra_conv`)  x bf16 as stored; the raw weights rounded once to bf16
+ *            by the pack (BatchNorm is NOT folded into them); products of two bf16 values accumulated in fp32; epilogue
+ *            relu(acc * scale + shift) in fp32 (scale / shift of the folded eval BatchNorm, NULL = 1 / 0); bf16 store;
+ *   summation order a function of the rulebook only (no float atomics, no hipMemsetAsync: the calls are captured into the
+ *            frame's hipGraph); two runs on the same inputs agree bit for bit.
+ * sassd_spconv_bf16_supported       (K, Cin, Cout) in {(27,4,16), (27|1, 16,16), (27|1, 16,32), (27|1, 32,32), (27|1, 32,64),
+ *                                   (27|1, 64,64)} and 0 < cap < 2^25 (every layer of the trunk at car batch 1, multi_cfg batch 8
+ *                                   and Waymo-scale batch 4).
+ * sassd_spconv_bf16_pack_weight     w [K,Cin,Cout] fp32 -> an opaque image of sassd_spconv_bf16_packed_bytes bytes (0: no kernel
+ *                                   for the shape), 16-byte aligned: bf16 for Cin >= 16, the fp32 image of
+ *                                   sassd_spconv_pack_weight for Cin = 4.
+ * sassd_spconv_fwd_bf16             y_bf16 [cap_out, Cout] = the layer above; x bf16 [rows, Cin], or fp32 [rows, 4] with
+ *                                   x_is_f32 = 1 (legal, and required, for Cin = 4 only); nbr NULL = identity rulebook with K = 1.
+ *                                   x, w_packed, scale, shift 16-byte, y 8-byte aligned.  cfg is reserved (0): the fp32 kernel
+ *                                   selection words do not apply.
+ * sassd_densify_from_bf16           densify of bf16 features [rows, C]: the bits copied into a bf16 map (out_is_bf16 = 1) or
+ *                                   widened exactly into an fp32 map; supported as sassd_densify_bf16, out 16-byte aligned,
+ *                                   cleared by a fill kernel.
+ * Every entry point returns SASSD_EINVAL for a NULL / misaligned pointer or an unsupported shape before it touches the device.
+ * ---------------------------------------------------------------------------------------------- */
+int sassd_spconv_bf16_supported(int K, int Cin, int Cout, int cap);
+size_t sassd_spconv_bf16_packed_bytes(int K, int Cin, int Cout);
+int sassd_spconv_bf16_pack_weight(const float *w, int K, int Cin, int Cout, void *packed, void *stream);
+int sassd_spconv_fwd_bf16(const void *x, int x_is_f32, const int32_t *nbr, const int32_t *n_out_ptr, int cap_out,
+                          const void *w_packed, int K, int Cin, int Cout, const float *scale, const float *shift, int relu,
+                          void *y_bf16, int cfg, void *stream);
+int sassd_densify_from_bf16(const void *feats, const int32_t *indices, const int32_t *n_ptr, int cap, int C, int D, int H, int W,
+                            int batch_size, int channel_order, void *out, int out_is_bf16, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * (a9,a10,a12) Dense 2-D convolution (3x3 pad 1 or 1x1), NCHW fp32, on fp32 MFMA (v_mfma_f32_32x32x2_f32),
  * fused per-channel affine (folded BatchNorm2d / bias) + optional ReLU.  Replaces torch.nn.Conv2d +
  * BatchNorm2d + ReLU in BEVNet (cmn.py:233-282), SSDRotateHead (ssd_rotate_head.py:120-125) and

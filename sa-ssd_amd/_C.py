@@ -63,6 +63,12 @@ _SIGS = {
     "sassd_densify": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "sassd_densify_bf16_supported": (_I, [_I, _I, _I, _I]),
     "sassd_densify_bf16": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    # bf16 sparse backbone (include/sassd.h "bf16 sparse backbone")
+    "sassd_spconv_bf16_supported": (_I, [_I, _I, _I, _I]),
+    "sassd_spconv_bf16_packed_bytes": (_SZ, [_I, _I, _I]),
+    "sassd_spconv_bf16_pack_weight": (_I, [_P, _I, _I, _I, _P, _P]),
+    "sassd_spconv_fwd_bf16": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P]),
+    "sassd_densify_from_bf16": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "sassd_conv2d_packed_floats": (_SZ, [_I, _I, _I]),
     "sassd_conv2d_pack_weight": (_I, [_P, _I, _I, _I, _P, _P]),
     "sassd_conv2d_fwd": (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),

@@ -492,6 +492,7 @@ spconv_gs_kernel(const float *__restrict__ x, const int32_t *__restrict__ nbr, c
 }
 
 #include "spconv_gq.h"
+#include "spconv_bf16.h"
 
 
 template <int CIN, int COUT, int RW, int NW, int CS, int WPS>
@@ -997,5 +998,80 @@ extern "C" int sassd_densify_bf16(const float *feats, const int32_t *indices, co
     if ((rc = sassd_launch_status())) return rc;
     hipLaunchKernelGGL(densify_bf16_kernel, dim3(cdiv(cap * C, 256)), dim3(256), 0, stream, feats, indices, n_ptr, cap, C, D,
                        H, W, channel_order, (unsigned short *)out);
+    return sassd_launch_status();
+}
+
+// ---- bf16 sparse backbone (InferencePlan(sparse_precision="bf16"); contract in include/sassd.h) ------------------------------
+extern "C" int sassd_spconv_bf16_supported(int K, int Cin, int Cout, int cap)
+{
+    if (cap <= 0 || cap >= (1 << 25)) return 0;              // packed pair-list entries: input row << 6 | local row
+    if (Cin == 4) return K == kK && Cout == 16;              // the first layer: fp32 in, bf16 out
+    const bool shape = (Cin == 16 && (Cout == 16 || Cout == 32)) || (Cin == 32 && (Cout == 32 || Cout == 64)) ||
+                       (Cin == 64 && Cout == 64);
+    return shape && (K == kK || K == 1);
+}
+
+extern "C" size_t sassd_spconv_bf16_packed_bytes(int K, int Cin, int Cout)
+{
+    if (!sassd_spconv_bf16_supported(K, Cin, Cout, 1)) return 0;
+    return (size_t)K * Cin * Cout * (Cin == 4 ? sizeof(float) : sizeof(unsigned short));
+}
+
+extern "C" int sassd_spconv_bf16_pack_weight(const float *w, int K, int Cin, int Cout, void *packed, void *stream_)
+{
+    if (!w || !packed || !sassd_spconv_bf16_supported(K, Cin, Cout, 1)) return SASSD_EINVAL;
+    if ((uintptr_t)packed & 15) return SASSD_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (Cin == 4) return launch_pack<4, 16>(w, K, (float *)packed, 0, stream);     // the fp32 image of sassd_spconv_pack_weight
+    const int total = K * Cin * Cout;
+    hipLaunchKernelGGL(pack_weight_bf16_kernel, dim3(cdiv(total, 256)), dim3(256), 0, stream, w, K, Cin, Cout,
+                       (unsigned short *)packed);
+    return sassd_launch_status();
+}
+
+extern "C" int sassd_spconv_fwd_bf16(const void *x, int x_is_f32, const int32_t *nbr, const int32_t *n_out_ptr, int cap_out,
+                                     const void *w_packed, int K, int Cin, int Cout, const float *scale, const float *shift,
+                                     int relu, void *y_bf16, int cfg, void *stream_)
+{
+    if (!x || !n_out_ptr || !w_packed || !y_bf16 || cfg != 0) return SASSD_EINVAL;
+    if (!sassd_spconv_bf16_supported(K, Cin, Cout, cap_out)) return SASSD_EINVAL;
+    if (nbr ? (K != kK) : (K != 1)) return SASSD_EINVAL;
+    if ((x_is_f32 != 0) != (Cin == 4)) return SASSD_EINVAL;  // fp32 operands exactly where the layer keeps them
+    if ((((uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)scale | (uintptr_t)shift) & 15) || ((uintptr_t)y_bf16 & 7))
+        return SASSD_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    const unsigned short *xb = (const unsigned short *)x, *wb = (const unsigned short *)w_packed;
+    unsigned short *y = (unsigned short *)y_bf16;
+    const int r = relu ? 1 : 0;
+    if (Cin == 4) return launch_c4<16, unsigned short>((const float *)x, nbr, n_out_ptr, cap_out, (const float *)w_packed, scale,
+                                                       shift, r, y, stream);
+    if (Cin == 16 && Cout == 16) return launch_bf16<16, 16>(xb, nbr, n_out_ptr, cap_out, wb, scale, shift, r, y, stream);
+    if (Cin == 16 && Cout == 32) return launch_bf16<16, 32>(xb, nbr, n_out_ptr, cap_out, wb, scale, shift, r, y, stream);
+    if (Cin == 32 && Cout == 32) return launch_bf16<32, 32>(xb, nbr, n_out_ptr, cap_out, wb, scale, shift, r, y, stream);
+    if (Cin == 32 && Cout == 64) return launch_bf16<32, 64>(xb, nbr, n_out_ptr, cap_out, wb, scale, shift, r, y, stream);
+    if (Cin == 64 && Cout == 64) return launch_bf16<64, 64>(xb, nbr, n_out_ptr, cap_out, wb, scale, shift, r, y, stream);
+    return SASSD_EINVAL;
+}
+
+extern "C" int sassd_densify_from_bf16(const void *feats, const int32_t *indices, const int32_t *n_ptr, int cap, int C, int D,
+                                       int H, int W, int batch_size, int channel_order, void *out, int out_is_bf16,
+                                       void *stream_)
+{
+    if (!feats || !indices || !n_ptr || !out || cap <= 0 || batch_size < 1 || !sassd_densify_bf16_supported(C, D, H, W))
+        return SASSD_EINVAL;
+    if ((uintptr_t)out & 15) return SASSD_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc;
+    // a fill kernel, never hipMemsetAsync (a memset node in a captured frame graph)
+    const size_t obytes = (size_t)batch_size * C * D * H * W * (out_is_bf16 ? sizeof(unsigned short) : sizeof(float));
+    if ((rc = sassd_fill2(out, obytes, 0, out, 0, 0, stream))) return rc;
+    if ((rc = sassd_launch_status())) return rc;
+    const unsigned short *f = (const unsigned short *)feats;
+    if (out_is_bf16)
+        hipLaunchKernelGGL(densify_from_bf16_kernel<unsigned short>, dim3(cdiv(cap * C, 256)), dim3(256), 0, stream, f, indices,
+                           n_ptr, cap, C, D, H, W, channel_order, (unsigned short *)out);
+    else
+        hipLaunchKernelGGL(densify_from_bf16_kernel<float>, dim3(cdiv(cap * C, 256)), dim3(256), 0, stream, f, indices, n_ptr,
+                           cap, C, D, H, W, channel_order, (float *)out);
     return sassd_launch_status();
 }

@@ -438,11 +438,13 @@ int launch_pw(const float *x, const int32_t *n_ptr, int cap, const float *wp, co
 // IS that layout), k ascending -- a fixed summation order.  Latency is hidden by occupancy (few registers, no LDS
 // beyond the 6.9 KB of weights), not by a software pipeline.
 // ------------------------------------------------------------------------------------------------------------------
-template <int COUT>
+// TY = unsigned short: the first layer of the bf16 sparse backbone (fp32 operands and accumulation, the result rounded to bf16
+// at the store); TY = float is the fp32 layer, unchanged.
+template <int COUT, typename TY = float>
 __global__ void __launch_bounds__(256)
 spconv_c4_kernel(const float *__restrict__ x, const int32_t *__restrict__ nbr, const int32_t *__restrict__ n_ptr, int cap,
                  const float *__restrict__ wp, const float *__restrict__ scale, const float *__restrict__ shift, int relu,
-                 float *__restrict__ y)
+                 TY *__restrict__ y)
 {
     __shared__ float4 ws[kK * COUT];
     for (int i = threadIdx.x; i < kK * COUT; i += 256) ws[i] = ((const float4 *)wp)[i];
@@ -464,14 +466,15 @@ spconv_c4_kernel(const float *__restrict__ x, const int32_t *__restrict__ nbr, c
     }
     float o = acc * (scale ? scale[co] : 1.f) + (shift ? shift[co] : 0.f);
     if (relu) o = fmaxf(o, 0.f);
-    y[(size_t)row * COUT + co] = o;
+    if constexpr (std::is_same<TY, float>::value) y[(size_t)row * COUT + co] = o;
+    else y[(size_t)row * COUT + co] = __builtin_bit_cast(unsigned short, (__bf16)o);
 }
 
-template <int COUT>
+template <int COUT, typename TY = float>
 int launch_c4(const float *x, const int32_t *nbr, const int32_t *n_ptr, int cap, const float *wp, const float *scale,
-              const float *shift, int relu, float *y, hipStream_t stream)
+              const float *shift, int relu, TY *y, hipStream_t stream)
 {
-    hipLaunchKernelGGL((spconv_c4_kernel<COUT>), dim3(cdiv(cap * COUT, 256)), dim3(256), 0, stream, x, nbr, n_ptr, cap, wp,
+    hipLaunchKernelGGL((spconv_c4_kernel<COUT, TY>), dim3(cdiv(cap * COUT, 256)), dim3(256), 0, stream, x, nbr, n_ptr, cap, wp,
                        scale, shift, relu, y);
     return sassd_launch_status();
 }

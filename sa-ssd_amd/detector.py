@@ -896,8 +896,10 @@ class SingleStageDetector(nn.Module):
         fresh tensor per call, so the stacked tensor's address says nothing)."""
         # test_cfg['precision'] (optional, top level): "fp32" (default) or "bf16" -- InferencePlan(precision=...)
         precision = kw.pop('precision', None) or ((self.test_cfg or {}).get('precision') or 'fp32')
+        # test_cfg['sparse_precision'] (optional, top level): "fp32" (default) or "bf16" -- InferencePlan(sparse_precision=...)
+        sparse_precision = kw.pop('sparse_precision', None) or ((self.test_cfg or {}).get('sparse_precision') or 'fp32')
         key = (batch_size, str(device), K.weights_generation(),
-               sum(t._version for t in list(self.parameters()) + list(self.buffers())), precision)
+               sum(t._version for t in list(self.parameters()) + list(self.buffers())), precision, sparse_precision)
         an_t = anchors if torch.is_tensor(anchors) else torch.as_tensor(np.asarray(anchors))
         same = self._plan is not None and self._plan_key == key and self._plan.anchors.shape == an_t.reshape(-1, 7).shape
         fp = None
@@ -911,7 +913,7 @@ class SingleStageDetector(nn.Module):
             self._plan = InferencePlan(self.state_dict(), batch_size=batch_size, anchors=an.reshape(-1, 7),
                                        score_thr=tc.get('score_thr', 0.3),
                                        iou_thr=tc.get('nms', {}).get('iou_thr', 0.1), device=device, precision=precision,
-                                       **self._cfg, **kw)
+                                       sparse_precision=sparse_precision, **self._cfg, **kw)
             self._plan_key = key
         # (the source tensor is kept alive so that its id / address cannot be recycled by another tensor)
         self._plan_anchor_fp, self._plan_anchor_src = fp, anchors_src

@@ -376,6 +376,55 @@ def densify_bf16(feats, indices, n_ptr, cap, shape, batch_size, channel_order=0,
     return out
 
 
+# ---- bf16 sparse backbone (InferencePlan(sparse_precision="bf16")): bf16 features, fp32 accumulation and epilogue ---------------
+def spconv_bf16_supported(k, cin, cout, cap):
+    return bool(_C.lib().sassd_spconv_bf16_supported(k, cin, cout, cap))
+
+
+def spconv_bf16_pack_weight(w):
+    """w [K, Cin, Cout] fp32 (raw weights, no BatchNorm folded in) -> opaque image: bf16 for Cin >= 16, the fp32 image of
+    spconv_pack_weight for the 4-channel first layer (its operands stay fp32)."""
+    _chk_cuda(w)
+    k, cin, cout = w.shape
+    L = _C.lib()
+    nbytes = L.sassd_spconv_bf16_packed_bytes(k, cin, cout)
+    if not nbytes:
+        raise ValueError("no bf16 sparse-conv kernel for K=%d, %d -> %d" % (k, cin, cout))
+    packed = torch.empty(nbytes // 2, dtype=torch.int16, device=w.device)
+    _C.check(L.sassd_spconv_bf16_pack_weight(_C.ptr(w.contiguous()), k, cin, cout, _C.ptr(packed), _C.stream()),
+             "sassd_spconv_bf16_pack_weight")
+    return packed
+
+
+def spconv_fwd_bf16(x, nbr, n_out_ptr, cap_out, w_packed, k, cin, cout, scale=None, shift=None, relu=False, y=None):
+    """sparse conv with a bf16 store: x bf16 [rows, Cin] (fp32 [rows, 4] for the first layer), y bf16 [cap_out, Cout]."""
+    _chk_cuda(x, nbr, w_packed, scale, shift)
+    x_is_f32 = x.dtype == torch.float32
+    assert x.dtype in (torch.float32, torch.bfloat16) and x.is_contiguous()
+    if y is None:
+        y = torch.empty(cap_out, cout, dtype=torch.bfloat16, device=x.device)
+    assert y.dtype == torch.bfloat16 and y.is_contiguous()
+    _C.check(_C.lib().sassd_spconv_fwd_bf16(_C.ptr(x), 1 if x_is_f32 else 0, _C.ptr(nbr), _C.ptr(n_out_ptr), cap_out,
+                                            _C.ptr(w_packed), k, cin, cout, _C.ptr(scale), _C.ptr(shift), 1 if relu else 0,
+                                            _C.ptr(y), 0, _C.stream()), "sassd_spconv_fwd_bf16")
+    return y
+
+
+def densify_from_bf16(feats, indices, n_ptr, cap, shape, batch_size, channel_order=0, out=None, out_bf16=True):
+    """densify() of bf16 features: the bits copied into a bf16 map, or widened exactly into an fp32 map (fill kernel, no memset)."""
+    d, h, w = shape
+    c = feats.shape[1]
+    assert feats.dtype == torch.bfloat16
+    dt = torch.bfloat16 if out_bf16 else torch.float32
+    if out is None:
+        out = torch.empty(batch_size, c * d, h, w, dtype=dt, device=feats.device)
+    assert out.dtype == dt and out.is_contiguous()
+    _C.check(_C.lib().sassd_densify_from_bf16(_C.ptr(feats), _C.ptr(indices), _C.ptr(n_ptr), cap, c, d, h, w, batch_size,
+                                              channel_order, _C.ptr(out), 1 if out_bf16 else 0, _C.stream()),
+             "sassd_densify_from_bf16")
+    return out
+
+
 # --------------------------------------------------------------------------------------------------
 def conv2d_pack_weight(w):
     """w [Cout, Cin, k, k] f32 cuda (torch layout) -> packed [Cin/8][k*k][8][CoutPad]."""

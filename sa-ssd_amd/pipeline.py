@@ -23,6 +23,13 @@ the raw conv weights rounded once at construction (BatchNorm is not folded into 
 accumulator, relu(acc * scale + shift)), and the maps between two dense convs are stored as bf16 -- rounding at the store is
 the rounding the consumer would apply at its load.  Everything else (voxelizer, rulebooks, sparse convs, anchor mask, decode,
 PSWarp sampling, rescore / NMS) and the head / part-sensitive outputs it reads stay fp32.
+
+sparse_precision="bf16" (independent of `precision`) runs the 14 sparse convs on bf16 features: sassd_spconv_fwd_bf16 with weights
+from sassd_spconv_bf16_pack_weight.  The first layer (4 -> 16, voxel means in metres) keeps fp32 operands and stores bf16; every
+other layer reads bf16 features and raw weights rounded once to bf16, accumulates in fp32, applies relu(acc * scale + shift) in
+fp32 and stores bf16.  The feature ping-pong buffers (and `middle`) hold bf16; densify copies the level-3 features unchanged into
+the bf16 map, or widens them exactly into the fp32 one (sassd_densify_from_bf16).  Voxels, rulebooks and anchor masks are those of
+the fp32 plan.
 """
 import numpy as np
 
@@ -73,13 +80,19 @@ class InferencePlan:
                  anchors_per_loc=2, grid_offsets=(0., 40.), featmap_stride=0.4, rpn_thr=0.1, score_thr=0.3,
                  iou_thr=0.1, cap_k=4096, cap_d=512, device=None, level_cap_factor=2, overlap=True, winograd=True,
                  fused_rulebooks=True, chain_bev=True, pyramid_persistent=False, spconv_cfg=None, wino4_cfg=None,
-                 skip_inactive_tiles=True, rb_sync_levels=(0, 1, 2, 3), ps_tail=False, precision="fp32"):
+                 skip_inactive_tiles=True, rb_sync_levels=(0, 1, 2, 3), ps_tail=False, precision="fp32",
+                 sparse_precision="fp32"):
         """precision: "fp32" (default) or "bf16" (module docstring).  In bf16 mode the fp32 kernel-selection knobs
         (winograd, chain_bev, wino4_cfg, ps_tail, skip_inactive_tiles) are ignored, and a shape the bf16 kernels do not
-        support raises ValueError here (there is no fp32 fall-back)."""
+        support raises ValueError here (there is no fp32 fall-back).
+        sparse_precision: "fp32" (default) or "bf16" -- the 14 sparse convs on bf16 features (module docstring), independent
+        of `precision`; spconv_cfg selects among the fp32 sparse kernels only."""
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32' or 'bf16', got %r" % (precision,))
+        if sparse_precision not in ("fp32", "bf16"):
+            raise ValueError("sparse_precision must be 'fp32' or 'bf16', got %r" % (sparse_precision,))
         self.precision, self.bf16 = precision, precision == "bf16"
+        self.sparse_precision, self.sparse_bf16 = sparse_precision, sparse_precision == "bf16"
         dev = torch.device(device if device is not None else "cuda:0")
         self.dev, self.B, self.ncls, self.A = dev, int(batch_size), int(num_class), int(anchors_per_loc)
         self.voxel_size = np.asarray(voxel_size, np.float32)
@@ -103,12 +116,24 @@ class InferencePlan:
 
         # ---- sparse weights -----------------------------------------------------------------------
         self.sp = []
+        lvl = 0
         for wname, bnname, kind, cin, cout, key in VXNET:
             w = sd["neck.backbone.%s.weight" % wname].float()
             k = 1 if kind == "1x1" else 27
-            wp = K.spconv_pack_weight(w.reshape(k, cin, cout).contiguous())
+            lvl += kind == "down"
+            if self.sparse_bf16:
+                # the raw weights rounded once to bf16 (the first layer keeps fp32 operands); BatchNorm stays in the epilogue
+                if not K.spconv_bf16_supported(k, cin, cout, self.caps[lvl]):
+                    raise ValueError("sparse_precision='bf16': %s (%s, %d -> %d) at a capacity of %d rows is not supported by "
+                                     "the bf16 sparse-conv kernels" % (wname, kind, cin, cout, self.caps[lvl]))
+                wp = K.spconv_bf16_pack_weight(w.reshape(k, cin, cout).contiguous())
+            else:
+                wp = K.spconv_pack_weight(w.reshape(k, cin, cout).contiguous())
             scale, shift = fold_bn(sd, "neck.backbone.%s" % bnname)
             self.sp.append((kind, cin, cout, key, wp, scale, shift))
+        if self.sparse_bf16 and not K.densify_bf16_supported(64, self.shapes[3]):
+            raise ValueError("sparse_precision='bf16': the dense map (64 x %d channels) on a %dx%d BEV map is not supported by "
+                             "the bf16 densify" % (D3, self.H, self.W))
 
         # ---- dense weights ------------------------------------------------------------------------
         hw = torch.cat([sd["rpn_head.conv_box.weight"], sd["rpn_head.conv_cls.weight"],
@@ -153,7 +178,8 @@ class InferencePlan:
         self.nbr = {key: z(self.caps[lvl], 27, dt=i32)
                     for key, lvl in (("subm0", 0), ("down0", 1), ("subm1", 1), ("down1", 2), ("subm2", 2),
                                      ("down2", 3), ("subm3", 3))}
-        self.feat = [z(max(self.caps), 64), z(max(self.caps), 64)]
+        fdt = torch.bfloat16 if self.sparse_bf16 else f32   # sparse feature ping-pong (sparse bf16 mode: rounded at the store)
+        self.feat = [z(max(self.caps), 64, dt=fdt), z(max(self.caps), 64, dt=fdt)]
         self.mean = z(self.caps[0], 4)
         mdt = torch.bfloat16 if self.bf16 else f32          # maps read by a dense conv (bf16 mode: rounded at the store)
         self.dense = z(B, 64 * D3, H, W, dt=mdt)
@@ -196,6 +222,7 @@ class InferencePlan:
         self.rb_sync_levels = tuple(sorted(int(l) for l in rb_sync_levels))   # levels whose completion the main stream waits
         assert self.rb_sync_levels and self.rb_sync_levels[-1] == 3           # for ((0, 1, 2, 3): one wait per level)
         self.prof = None           # set to {} to collect (name, start_event, end_event) tuples per frame
+        self.prof_sparse_layers = False     # with prof: also one segment per sparse conv (sparse_conv0..13)
 
     def _dense_weights_fp32(self, sd, hw, w0, w1, winograd, chain_bev, wino4_cfg, ps_tail):
         """precision="fp32": BEVNet on Winograd / fp32-MFMA kernels with BatchNorm folded into the epilogues, the heads on the
@@ -398,11 +425,17 @@ class InferencePlan:
                 upto = min([l for l in self.rb_sync_levels if l >= lvl] or [3])
                 main.wait_event(self.rb_ev["subm%d" % upto])
                 covered = upto
-            if kind == "subm" or kind == "down":
+            el = self._ev() if self.prof is not None and self.prof_sparse_layers else None
+            if self.sparse_bf16:
+                K.spconv_fwd_bf16(x, None if key is None else self.nbr[key], self.n[lvl], self.caps[lvl], wp,
+                                  1 if key is None else 27, cin, cout, scale, shift, True, y)
+            elif kind == "subm" or kind == "down":
                 K.spconv_fwd(x, self.nbr[key], self.n[lvl], self.caps[lvl], wp, 27, cin, cout, scale, shift, True, y,
                              cfg=self.spconv_cfg)
             else:
                 K.spconv_fwd(x, None, self.n[lvl], self.caps[lvl], wp, 1, cin, cout, scale, shift, True, y, cfg=self.spconv_cfg)
+            if el is not None:
+                self._seg("sparse_conv%d" % li, el)
             if keep_middle:
                 self.middle[li] = (y.clone(), lvl, cout)
             x = y
@@ -412,7 +445,9 @@ class InferencePlan:
         if not densify:
             return
         e1 = self._ev() if self.prof is not None else None
-        if self.bf16:
+        if self.sparse_bf16:            # the bf16 features unchanged: copied into a bf16 map, widened exactly into an fp32 one
+            K.densify_from_bf16(x, self.idx[3], self.n[3], self.caps[3], self.shapes[3], self.B, 1, self.dense, out_bf16=self.bf16)
+        elif self.bf16:
             K.densify_bf16(x, self.idx[3], self.n[3], self.caps[3], self.shapes[3], self.B, 1, self.dense)
         else:
             K.densify(x, self.idx[3], self.n[3], self.caps[3], self.shapes[3], self.B, 1, self.dense)

@@ -1,11 +1,14 @@
-"""bf16 against fp32 inference on the same weights, in one process (InferencePlan(precision=...)).
+"""bf16 against fp32 inference on the same weights, in one process (InferencePlan(precision=..., sparse_precision=...)).
 
-For each workload (car batch 1, multi_cfg batch 8) an fp32 and a bf16 plan are built from the bench model (bench.build_model) and
-measured alternately, `--repeats` times each:
+For each workload (car batch 1, multi_cfg batch 8) four plans are built from the bench model (bench.build_model) -- fp32, bf16 dense
+convs, bf16 dense convs + bf16 sparse backbone, fp32 dense convs + bf16 sparse backbone (PLANS) -- and measured in turn,
+`--repeats` times each:
   * sequential frames/s: one plan's captured frame (two-branch graph) replayed `--steps` times back to back;
   * frames in flight: three one-branch plans on three streams (bench.py's form);
   * the BEV stage: per-layer events of plan.prof (bev_conv0..7) and the heads (fused SSD head + both part-sensitive convs), on
-    eager frames.
+    eager frames;
+  * the sparse stage: the `sparse` segment of plan.prof (rulebook pyramid waits + 14 sparse convs), and each sparse conv on its
+    own (sparse_conv0..13, plan.prof_sparse_layers: events between the launches, on separate eager frames).
 One JSON record: median and min..max over the repeats per figure, the bf16 / fp32 ratios, and the largest difference per detection
 field between the two plans on the same seeded frames (count, boxes, scores, labels of the detections both plans keep).
 
@@ -27,9 +30,14 @@ import bench  # noqa: E402
 from sassd.pipeline import InferencePlan  # noqa: E402
 
 
-def _plan(sd, w, dev, precision, overlap=True):
+# plan name -> (precision, sparse_precision): the dense convs and the sparse backbone choose independently
+PLANS = {"fp32": ("fp32", "fp32"), "bf16": ("bf16", "fp32"), "bf16_sparse": ("bf16", "bf16"), "fp32_dense_bf16_sparse": ("fp32", "bf16")}
+
+
+def _plan(sd, w, dev, name, overlap=True):
+    precision, sparse_precision = PLANS[name]
     return InferencePlan(sd, batch_size=w["batch"], anchors=w["anchors"], anchors_bv=w["anchors_bv"], device=dev,
-                         overlap=overlap, precision=precision, **w["plan"])
+                         overlap=overlap, precision=precision, sparse_precision=sparse_precision, **w["plan"])
 
 
 def _spread(v):
@@ -78,9 +86,16 @@ def _stage_ms(plan, batch, frames=10):
         plan.run_from_points(batch)
     torch.cuda.synchronize()
     out = {k: statistics.median(a.elapsed_time(b) for a, b in v) for k, v in plan.prof.items()}
-    plan.prof = None
+    # the sparse segment (rulebook waits included) on frames without per-layer events, then each sparse conv on its own
+    plan.prof_sparse_layers = True
+    for _ in range(frames):
+        plan.run_from_points(batch)
+    torch.cuda.synchronize()
+    out.update({k: statistics.median(a.elapsed_time(b) for a, b in v) for k, v in plan.prof.items() if k.startswith("sparse_conv")})
+    plan.prof, plan.prof_sparse_layers = None, False
     out["bev"] = sum(v for k, v in out.items() if k.startswith("bev_conv"))
     out["bev+heads"] = out["bev"] + out.get("heads", 0.0)
+    out["sparse_convs"] = sum(v for k, v in out.items() if k.startswith("sparse_conv") and k != "sparse_convs")
     return out
 
 
@@ -112,7 +127,7 @@ def measure(config, dev, steps, warmup, repeats):
 
     def batch_of(i):
         return [clouds[(i * B + j) % len(clouds)] for j in range(B)]
-    precs = ("fp32", "bf16")
+    precs = tuple(PLANS)
     seq = {p: _plan(sd, w, dev, p) for p in precs}
     fly = {p: [_plan(sd, w, dev, p, overlap=False) for _ in range(3)] for p in precs}
     eager = {p: _plan(sd, w, dev, p) for p in precs}
@@ -134,34 +149,51 @@ def measure(config, dev, steps, warmup, repeats):
             res[p] = _detections(eager[p])
             assert int(eager[p].status.item()) == 0, (p, "status 0x%x" % int(eager[p].status.item()))
             counts[p] += sum(0 if r[0] is None else len(r[0]) for r in res[p])
-        diffs.append(_det_diff(res["fp32"], res["bf16"]))
-    det = dict(count=max(d["count"] for d in diffs), boxes=list(np.max([d["boxes"] for d in diffs], 0)),
-               scores=max(d["scores"] for d in diffs), labels_differ=sum(d["labels_differ"] for d in diffs),
-               detections=counts, frames=4 * B)
-    figs = {p: dict(seq=[], inflight=[], bev=[], bev_heads=[], layers={}) for p in precs}
+        diffs.append({p: _det_diff(res["fp32"], res[p]) for p in precs if p != "fp32"})
+
+    def det_of(p):
+        d_ = [d[p] for d in diffs]
+        return dict(count=max(d["count"] for d in d_), boxes=list(np.max([d["boxes"] for d in d_], 0)),
+                    scores=max(d["scores"] for d in d_), labels_differ=sum(d["labels_differ"] for d in d_),
+                    detections=dict(fp32=counts["fp32"], **{p: counts[p]}), frames=4 * B)
+    figs = {p: dict(seq=[], inflight=[], bev=[], bev_heads=[], sparse=[], sparse_convs=[], layers={}) for p in precs}
     for r in range(repeats):
         for p in (precs if r % 2 == 0 else precs[::-1]):          # alternate the order: no drift favours one side
             f = figs[p]
             st = _stage_ms(eager[p], batch_of(r))
             f["bev"].append(st["bev"])
             f["bev_heads"].append(st["bev+heads"])
+            f["sparse"].append(st["sparse"])
+            f["sparse_convs"].append(st["sparse_convs"])
             for k, v in st.items():
-                if k.startswith("bev_conv") or k in ("heads", "densify"):
+                if k.startswith("bev_conv") or k.startswith("sparse_conv") or k in ("heads", "densify"):
                     f["layers"].setdefault(k, []).append(v)
             f["seq"].append(_fps_sequential(seq[p], batch_of, steps, warmup))
             f["inflight"].append(_fps_inflight(fly[p], streams, batch_of, steps, warmup))
     out = dict(workload=config, batch=B, repeats=repeats, steps=steps)
     for p in precs:
         f = figs[p]
-        out[p] = dict(fps_sequential=_spread(f["seq"]), fps_inflight3=_spread(f["inflight"]), bev_ms=_spread(f["bev"]),
-                      bev_heads_ms=_spread(f["bev_heads"]),
+        out[p] = dict(precision=PLANS[p][0], sparse_precision=PLANS[p][1], fps_sequential=_spread(f["seq"]),
+                      fps_inflight3=_spread(f["inflight"]), bev_ms=_spread(f["bev"]), bev_heads_ms=_spread(f["bev_heads"]),
+                      sparse_ms=_spread(f["sparse"]), sparse_convs_ms=_spread(f["sparse_convs"]),
                       layers_ms={k: statistics.median(v) for k, v in sorted(f["layers"].items())})
     med = lambda p, k: out[p][k]["median"]      # noqa: E731
     out["bf16_over_fp32"] = dict(bev_speedup=med("fp32", "bev_ms") / med("bf16", "bev_ms"),
                                  bev_heads_speedup=med("fp32", "bev_heads_ms") / med("bf16", "bev_heads_ms"),
                                  fps_sequential=med("bf16", "fps_sequential") / med("fp32", "fps_sequential"),
                                  fps_inflight3=med("bf16", "fps_inflight3") / med("fp32", "fps_inflight3"))
-    out["detections_bf16_vs_fp32"] = det
+    # the bf16 sparse backbone against the fp32 one, on plans whose dense convs are the same
+    for p, base in (("bf16_sparse", "bf16"), ("fp32_dense_bf16_sparse", "fp32")):
+        out["%s_over_%s" % (p, base)] = dict(
+            sparse_speedup=med(base, "sparse_ms") / med(p, "sparse_ms"),
+            sparse_convs_speedup=med(base, "sparse_convs_ms") / med(p, "sparse_convs_ms"),
+            fps_sequential=med(p, "fps_sequential") / med(base, "fps_sequential"),
+            fps_inflight3=med(p, "fps_inflight3") / med(base, "fps_inflight3"),
+            layer_speedup={"sparse_conv%d" % i: out[base]["layers_ms"]["sparse_conv%d" % i] / out[p]["layers_ms"]["sparse_conv%d" % i]
+                           for i in range(14)})
+    out["detections_bf16_vs_fp32"] = det_of("bf16")
+    out["detections_bf16_sparse_vs_fp32"] = det_of("bf16_sparse")
+    out["detections_fp32_dense_bf16_sparse_vs_fp32"] = det_of("fp32_dense_bf16_sparse")
     return out
 
 
