@@ -7,6 +7,7 @@ import torch
 from torch.autograd import Function
 
 from . import kernels as K
+from . import weight_images as WI
 
 
 _BEV_PRECISION = "fp32"
@@ -58,52 +59,14 @@ def _ident_nbr(n, dev):
     return t[:n]
 
 
-class _PackCache(dict):
-    """Packed-weight images keyed by the source weight's (address, shape, ...) and validated by its generation
-    (kernels.weight_key: version counter, address, device, global generation).  A FRESH tensor can land on the address of a
-    dead one with the same shape, version 0 and the same global generation -- its key and generation then equal the dead
-    tensor's and the lookup would return the dead tensor's image (round 5: the sparse data gradient of the third 64 -> 64 layer
-    a test created was computed with the first one's transposed weights; models built through build_detector bump the
-    generation, hand-made layers and tests do not).  So an entry PINS the tensor it was packed from: while the entry exists
-    that storage cannot be freed, hence no other tensor can sit on its address.  Bounded, LEAST RECENTLY USED first (ADVICE r05:
-    insertion order dropped the long-lived parameter packs a PackPlan installs first once 256 transient keys had piled up):
-    every hit and every put moves the key to the young end; a dropped entry only costs a re-pack."""
-    MAX = 256
-
-    def get(self, key, default=None):
-        hit = dict.get(self, key, default)
-        if hit is not default and key in self:
-            dict.__delitem__(self, key)                     # re-insert: dicts keep insertion order, the front is the oldest
-            dict.__setitem__(self, key, hit)
-        return hit
-
-    def put(self, key, gen, pack, source):
-        if key in self:
-            dict.__delitem__(self, key)
-        elif len(self) >= self.MAX:
-            for k in list(self)[:self.MAX // 4]:
-                dict.__delitem__(self, k)
-        self[key] = (gen, pack, source)
-
-
-_sp_t_packs = _PackCache()
-
-
 def _spconv_t_pack(weight, reverse=False):
-    """Transposed packed image of a sparse-conv weight [K, Cin, Cout] for the data gradient, cached per parameter
-    storage and weight generation (sassd.train.PackPlan refreshes the entry right after the optimizer step).
-    reverse: the image of offset k holds W[K-1-k]^T (submanifold layers, see SparseConvFn.backward)."""
-    key = (weight.data_ptr(), tuple(weight.shape)) + ((True,) if reverse else ())
-    gen = K.weight_key(weight)
-    hit = _sp_t_packs.get(key)
-    if hit is not None and hit[0] == gen:
-        return hit[1]
-    w = weight.detach()
-    pack = K.spconv_pack_weight_t((w.flip(0) if reverse else w).contiguous())
-    # the entry pins the STORAGE (so that no other tensor can land on the address), not the autograd graph: the weight handed
-    # in is a view of the module parameter (grad_fn = a view node) -- pinning it would keep that graph alive (ADVICE r05)
-    _sp_t_packs.put(key, gen, pack, w if weight.grad_fn is not None else weight)
-    return pack
+    """Transposed packed image of a sparse-conv weight [K, Cin, Cout] for the data gradient (sassd.train.PackPlan refreshes
+    it right after the optimizer step).  reverse: the image of offset k holds W[K-1-k]^T (submanifold layers, see
+    SparseConvFn.backward)."""
+    def build():
+        w = weight.detach()
+        return K.spconv_pack_weight_t((w.flip(0) if reverse else w).contiguous())
+    return WI.image(weight, "spconv_t_rev" if reverse else "spconv_t", build)
 
 
 class SparseConvFn(Function):
@@ -189,46 +152,21 @@ def _conv_any(x, weight, ks, packed=None, wino=None, shift=None, wino4=None):
 # channel pairs the sparse kernels are instantiated for (csrc/spconv.hip SP_DISPATCH); anything else takes the GEMM
 _SP_PAIRS = {(4, 16), (16, 16), (16, 32), (32, 32), (32, 64), (64, 64), (32, 16), (64, 32)}
 
-_dgrad_packs = _PackCache()
-_dgrad_direct = {}
-
-
-def _cacheable(weight):
-    """Packed images are cached per parameter STORAGE and weight generation.  A derived tensor (the fused RPN head's
-    `torch.cat` of three conv weights: fresh storage every step, `_version` always 0, and the caching allocator hands the
-    same address back) has no generation of its own -- after load_state_dict / a torch.optim step / an in-place edit of
-    its sources its cached image would be silently stale: such weights are packed on every call."""
-    return weight.is_leaf and weight.grad_fn is None
-
 
 def _dgrad_pack(weight, h, w):
-    """Packed image of the data-gradient conv's weights (transposed, taps mirrored), cached per parameter storage and
-    weight generation: the pack is a pure function of the weights, which change once per optimizer step."""
+    """fp32 image of the data-gradient conv's weights (transposed, taps mirrored): dict(wino4 | wino | packed, wt).  Which
+    form a 3x3 layer takes depends on the map size; a 1x1 layer's does not (PackPlan installs it under the same key)."""
     ks = weight.shape[2]
-    gen = K.weight_key(weight)
-    cache = _cacheable(weight)
-    hit = _dgrad_direct.get((weight.data_ptr(), tuple(weight.shape))) if cache else None   # installed by sassd.train.PackPlan
-    if hit is not None and hit[0] == gen:
-        return hit[1]
-    key = (weight.data_ptr(), tuple(weight.shape), h, w)
-    hit = _dgrad_packs.get(key) if cache else None
-    if hit is not None and hit[0] == gen:
-        return hit[1]
-    wt = weight.detach().transpose(0, 1).flip(2, 3).contiguous()          # [Cin, Cout, k, k]
-    cin_g, cout_g = wt.shape[1], wt.shape[0]
-    if ks == 3 and K.conv2d_wino4_supported(cin_g, cout_g, h, w):
-        pack = dict(wino4=K.conv2d_wino4_pack_weight(wt))
-    elif ks == 3 and K.conv2d_wino_supported(cin_g, cout_g, h, w):
-        pack = dict(wino=K.conv2d_wino_pack_weight(wt))
-    else:
-        pack = dict(packed=K.conv2d_pack_weight(wt))
-    pack["wt"] = wt
-    if cache:
-        _dgrad_packs.put(key, gen, pack, weight)
-    return pack
 
-
-_bf16_packs = _PackCache()
+    def build():
+        wt = weight.detach().transpose(0, 1).flip(2, 3).contiguous()          # [Cin, Cout, k, k]
+        cin_g, cout_g = wt.shape[1], wt.shape[0]
+        if ks == 3 and K.conv2d_wino4_supported(cin_g, cout_g, h, w):
+            return dict(wino4=K.conv2d_wino4_pack_weight(wt), wt=wt)
+        if ks == 3 and K.conv2d_wino_supported(cin_g, cout_g, h, w):
+            return dict(wino=K.conv2d_wino_pack_weight(wt), wt=wt)
+        return dict(packed=K.conv2d_pack_weight(wt), wt=wt)
+    return WI.image(weight, "dgrad", build, (h, w) if ks == 3 else ())
 
 
 def bf16_cout_pad(cout):
@@ -240,40 +178,21 @@ def bf16_cout_pad(cout):
 
 def _bf16_pack(weight, transposed):
     """bf16 [tap][Cin/8][Cout][8] image of the weights (forward; Cout zero-padded to a multiple of 32) or of their transposed,
-    tap-mirrored form (data gradient), cached per parameter storage and weight generation like _dgrad_pack."""
-    key = (weight.data_ptr(), tuple(weight.shape), transposed)
-    gen = K.weight_key(weight)
-    cache = _cacheable(weight)
-    hit = _bf16_packs.get(key) if cache else None
-    if hit is not None and hit[0] == gen:
-        return hit[1]
-    w = weight.detach()
-    if transposed:
-        w = w.transpose(0, 1).flip(2, 3)
-    elif w.shape[0] % 32:
-        w = torch.cat([w, w.new_zeros((bf16_cout_pad(w.shape[0]) - w.shape[0],) + tuple(w.shape[1:]))], 0)
-    pack = K.conv2d_bf16_pack_weight(w.contiguous())
-    if cache:
-        _bf16_packs.put(key, gen, pack, weight)
-    return pack
-
-
-_bf16_1x1_packs = _PackCache()
+    tap-mirrored form (data gradient)."""
+    def build():
+        w = weight.detach()
+        if transposed:
+            w = w.transpose(0, 1).flip(2, 3)
+        elif w.shape[0] % 32:
+            w = torch.cat([w, w.new_zeros((bf16_cout_pad(w.shape[0]) - w.shape[0],) + tuple(w.shape[1:]))], 0)
+        return K.conv2d_bf16_pack_weight(w.contiguous())
+    return WI.image(weight, "bf16_3x3_t" if transposed else "bf16_3x3", build)
 
 
 def _bf16_pack_1x1(weight, transposed):
-    """bf16 MFMA-fragment image of a 1x1 conv's weights (forward) or of their transpose (data gradient), cached like
-    _bf16_pack (sassd.train.PackPlan refreshes the entries of the module parameters after the optimizer step)."""
-    key = (weight.data_ptr(), tuple(weight.shape), transposed)
-    gen = K.weight_key(weight)
-    cache = _cacheable(weight)
-    hit = _bf16_1x1_packs.get(key) if cache else None
-    if hit is not None and hit[0] == gen:
-        return hit[1]
-    pack = K.conv1x1_bf16_pack_weight(weight.detach(), transposed)
-    if cache:
-        _bf16_1x1_packs.put(key, gen, pack, weight)
-    return pack
+    """bf16 MFMA-fragment image of a 1x1 conv's weights (forward) or of their transpose (data gradient)."""
+    return WI.image(weight, "bf16_1x1_t" if transposed else "bf16_1x1",
+                    lambda: K.conv1x1_bf16_pack_weight(weight.detach(), transposed))
 
 
 class Conv2dFn(Function):

@@ -24,6 +24,7 @@ from . import iou3d_utils
 from . import kernels as K
 from . import spconv
 from . import train_ops as T
+from . import weight_images
 from .autograd import bf16_cout_pad, bn_relu_conv, bn_relu_conv_fusable, AuxHeadFn, Conv2dFn, FocalLossFn, GuidedDecodeFn, PSWarpBatchFn, PSWarpFn, RpnLossFn, bev_precision, bn_relu_2d
 from .config import _wrap, obj_from_dict
 from .kitti_common import kitti_bbox2results
@@ -213,29 +214,23 @@ class _HipConv2d(nn.Conv2d):
         K.bump_weights_generation()
         return out
 
+    def _image(self, kind, pack):
+        return weight_images.image(self.weight, kind, lambda: pack(self.weight.detach().float().contiguous()))
+
     def packed_weight(self):
-        v = K.weight_key(self.weight)
-        if getattr(self, "_pk", None) is None or self._pkv != v:
-            self._pk, self._pkv = K.conv2d_pack_weight(self.weight.detach().float().contiguous()), v
-        return self._pk
+        return self._image("direct", K.conv2d_pack_weight)
 
     def packed_wino(self, h, w):
         """Winograd-packed weights when this layer / feature-map shape supports the F(2x2,3x3) kernel, else None."""
         if self.kernel_size[0] != 3 or not K.conv2d_wino_supported(self.in_channels, self.out_channels, h, w):
             return None
-        v = K.weight_key(self.weight)
-        if getattr(self, "_pkw", None) is None or self._pkwv != v:
-            self._pkw, self._pkwv = K.conv2d_wino_pack_weight(self.weight.detach().float().contiguous()), v
-        return self._pkw
+        return self._image("wino2", K.conv2d_wino_pack_weight)
 
     def packed_wino4(self, h, w):
         """Winograd F(4x4,3x3) weights (G g G^T, [36][Cin][Cout]) when the layer / feature-map shape supports it."""
         if self.kernel_size[0] != 3 or not K.conv2d_wino4_supported(self.in_channels, self.out_channels, h, w):
             return None
-        v = K.weight_key(self.weight)
-        if getattr(self, "_pk4", None) is None or self._pk4v != v:
-            self._pk4, self._pk4v = K.conv2d_wino4_pack_weight(self.weight.detach().float().contiguous()), v
-        return self._pk4
+        return self._image("wino4", K.conv2d_wino4_pack_weight)
 
     def hip_forward(self, x, scale=None, shift=None, relu=False):
         if shift is None and self.bias is not None:
@@ -246,22 +241,18 @@ class _HipConv2d(nn.Conv2d):
         pw = self.packed_wino(x.shape[2], x.shape[3])
         if pw is not None:
             return K.conv2d_wino_fwd(x.contiguous().float(), pw, self.out_channels, scale, shift, relu)
-        self.packed_weight()
-        if shift is None and self.bias is not None:
-            shift = self.bias.detach().float().contiguous()
-        return K.conv2d_fwd(x.contiguous().float(), self._pk, self.out_channels, self.kernel_size[0], scale, shift,
-                            relu)
+        return K.conv2d_fwd(x.contiguous().float(), self.packed_weight(), self.out_channels, self.kernel_size[0], scale,
+                            shift, relu)
 
     def forward(self, x):
         if torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad):
-            if (bev_precision() == "bf16" and self.kernel_size[0] == 3 and
-                    K.conv2d_bf16_supported(self.in_channels, bf16_cout_pad(self.out_channels), x.shape[2], x.shape[3])):
+            ks, h, w = self.kernel_size[0], x.shape[2], x.shape[3]
+            if bev_precision() == "bf16" and (
+                    K.conv2d_bf16_supported(self.in_channels, bf16_cout_pad(self.out_channels), h, w) if ks == 3 else
+                    ks == 1 and K.conv1x1_bf16_supported(self.in_channels, self.out_channels, h * w)):
                 return Conv2dFn.apply(x.float(), self.weight, self.bias, None, None, None)   # packs its own bf16 image
-            if (bev_precision() == "bf16" and self.kernel_size[0] == 1 and
-                    K.conv1x1_bf16_supported(self.in_channels, self.out_channels, x.shape[2] * x.shape[3])):
-                return Conv2dFn.apply(x.float(), self.weight, self.bias, None, None, None)   # (round 6) bf16 1x1 kernel
-            p4 = self.packed_wino4(x.shape[2], x.shape[3])
-            pw = None if p4 is not None else self.packed_wino(x.shape[2], x.shape[3])
+            p4 = self.packed_wino4(h, w)
+            pw = None if p4 is not None else self.packed_wino(h, w)
             pk = None if (p4 is not None or pw is not None) else self.packed_weight()
             return Conv2dFn.apply(x.float(), self.weight, self.bias, pk, pw, p4)
         return self.hip_forward(x)

@@ -8,8 +8,8 @@ from . import _C
 
 _ws_cache = {}
 
-# Packed-weight caches (SparseConvolution.packed_weight, _HipConv2d.packed_*, SingleStageDetector.plan) are keyed on
-# the parameter's autograd version AND on this generation: the fused optimizer and the checkpoint loaders write the
+# Cached weight images (sassd.weight_images, SingleStageDetector.plan) are validated by the parameter's autograd
+# version AND by this generation: the fused optimizer and the checkpoint loaders write the
 # flat parameter buffer through raw pointers / views, which never bumps `Tensor._version`.
 _weights_gen = [0]
 

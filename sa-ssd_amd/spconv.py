@@ -14,6 +14,7 @@ import torch
 from torch import nn
 
 from . import kernels as K
+from . import weight_images
 from .autograd import BnReluFn, DensifyFn, SparseConvFn, count_bn_batch, _n_ptr as _cached_n_ptr
 
 
@@ -69,8 +70,6 @@ class SparseConvolution(nn.Module):
         self.weight = nn.Parameter(torch.empty(*self.kernel_size, in_channels, out_channels))
         self.bias = nn.Parameter(torch.empty(out_channels)) if bias else None
         self.reset_parameters()
-        self._packed = None
-        self._packed_version = None
 
     def _apply(self, fn, *args, **kwargs):
         out = super()._apply(fn, *args, **kwargs)      # .to() / .cuda() on this layer alone: its packed image is stale
@@ -85,13 +84,11 @@ class SparseConvolution(nn.Module):
             self.bias.data.uniform_(-stdv, stdv)
 
     def packed_weight(self):
-        v = K.weight_key(self.weight)
-        if self._packed is None or self._packed_version != v:
+        def build():
             k = int(np.prod(self.kernel_size))
             w = self.weight.detach().reshape(k, self.in_channels, self.out_channels).contiguous().float()
-            self._packed = K.spconv_pack_weight(w)
-            self._packed_version = v
-        return self._packed
+            return K.spconv_pack_weight(w)
+        return weight_images.image(self.weight, "spconv", build)
 
     def _conv(self, feats, nbr, n_out, k, grad):
         """Raw conv (+bias) over a gather table: autograd-recording HIP path when gradients are wanted."""

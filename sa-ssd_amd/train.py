@@ -17,6 +17,7 @@ import torch
 import torch.distributed as dist
 
 from . import kernels as K
+from . import weight_images
 
 
 class FlatParams:
@@ -87,13 +88,14 @@ class PackPlan:
 
     def __init__(self, model, flat):
         import numpy as np
-        from . import autograd as AG, spconv as SP
+        from .autograd import SparseConvFn, bev_precision, bf16_cout_pad
         from .detector import _HipConv2d
+        from .spconv import SparseConvolution, SubMConv3d
         self.flat = flat
         dev = flat.data.device
         base = flat.data.data_ptr()
         f32_maps, bf_maps = [], []
-        self._f32, self._bf = [], []                  # (offset, numel, install(view))
+        self._f32, self._bf = [], []                  # (offset, numel, weight, image kind) of every image in the gather outputs
 
         def idx_like(p):
             """(flat index + 1) of every element of p, int32, shaped like p."""
@@ -105,12 +107,12 @@ class PackPlan:
             """int32 -> the same words typed fp32 (the pack kernels only move words, they never compute)."""
             return t.contiguous().view(torch.float32)
 
-        def add(maps, sinks, m, install):
-            sinks.append((sum(x.numel() for x in maps), m.numel(), install))
+        def add(maps, sinks, m, weight, kind):
+            sinks.append((sum(x.numel() for x in maps), m.numel(), weight, kind))
             maps.append(m.reshape(-1))
 
-        def add_f32(packed_bits, install):
-            add(f32_maps, self._f32, packed_bits.view(torch.int32) - 1, install)
+        def add_f32(packed_bits, weight, kind):
+            add(f32_maps, self._f32, packed_bits.view(torch.int32) - 1, weight, kind)
 
         def bf16_map(off, cout, cin, transposed):
             i = off + np.arange(cout * cin * 9, dtype=np.int64).reshape(cout, cin, 9)
@@ -118,7 +120,7 @@ class PackPlan:
                 i = i.transpose(1, 0, 2)[:, :, ::-1]
                 cout, cin = cin, cout
             cp = (cin + 31) // 32 * 32
-            co_p = cout if transposed else AG.bf16_cout_pad(cout)      # forward: zero rows up to a multiple of 32 output channels
+            co_p = cout if transposed else bf16_cout_pad(cout)      # forward: zero rows up to a multiple of 32 output channels
             pad = np.full((co_p, cp, 9), -1, np.int64)
             pad[:cout, :cin] = i
             cout = co_p
@@ -138,60 +140,33 @@ class PackPlan:
             assert idx.size == _C.lib().sassd_conv1x1_bf16_packed_elems(ci_n, co_n)
             return torch.from_numpy(idx.reshape(-1).astype(np.int32)).to(dev)
 
-        bf16 = AG.bev_precision() == "bf16"
+        bf16 = bev_precision() == "bf16"
         for m in model.modules():
-            if isinstance(m, SP.SparseConvolution) and m.weight.requires_grad:
+            if isinstance(m, SparseConvolution) and m.weight.requires_grad:
                 k = int(np.prod(m.kernel_size))
                 wi = bits(idx_like(m.weight).reshape(k, m.in_channels, m.out_channels))
-
-                def inst(view, m=m):
-                    m._packed, m._packed_version = view, K.weight_key(m.weight)
-                add_f32(K.spconv_pack_weight(wi), inst)
+                add_f32(K.spconv_pack_weight(wi), m.weight, "spconv")
                 if m.in_channels >= 16:
-                    key = (m.weight.data_ptr(), (k, m.in_channels, m.out_channels))
-
                     # submanifold layers differentiate on the forward rulebook with the offset-reversed image
-                    rev = isinstance(m, SP.SubMConv3d) and k == 27 and AG.SparseConvFn.subm_on_forward_table
-                    key = key + ((True,) if rev else ())
-
-                    def inst_t(view, m=m, key=key):
-                        AG._sp_t_packs[key] = (K.weight_key(m.weight), view, m.weight)
-                    add_f32(K.spconv_pack_weight_t(wi.flip(0).contiguous() if rev else wi), inst_t)
+                    rev = isinstance(m, SubMConv3d) and k == 27 and SparseConvFn.subm_on_forward_table
+                    add_f32(K.spconv_pack_weight_t(wi.flip(0).contiguous() if rev else wi),
+                            m.weight, "spconv_t_rev" if rev else "spconv_t")
             elif isinstance(m, _HipConv2d) and m.weight.requires_grad:
                 cout, cin, ks = m.out_channels, m.in_channels, m.kernel_size[0]
                 off = (m.weight.data_ptr() - base) // 4
-                wkey = (m.weight.data_ptr(), tuple(m.weight.shape))
-                direct_fwd = ks == 1
                 hw_any = 4                                   # (the shape test below does not depend on the map size)
-                c1_fwd = ks == 1 and bf16 and K.conv1x1_bf16_supported(cin, cout, hw_any)
-                c1_bwd = ks == 1 and bf16 and K.conv1x1_bf16_supported(cout, cin, hw_any)
-                if c1_fwd:
-                    def inst_c(view, m=m, wkey=wkey):
-                        AG._bf16_1x1_packs[wkey + (False,)] = (K.weight_key(m.weight), view, m.weight)
-                    add(bf_maps, self._bf, c1_map(off, cout, cin, False), inst_c)
-                if c1_bwd:
-                    def inst_ct(view, m=m, wkey=wkey):
-                        AG._bf16_1x1_packs[wkey + (True,)] = (K.weight_key(m.weight), view, m.weight)
-                    add(bf_maps, self._bf, c1_map(off, cout, cin, True), inst_ct)
+                if ks == 1 and bf16 and K.conv1x1_bf16_supported(cin, cout, hw_any):
+                    add(bf_maps, self._bf, c1_map(off, cout, cin, False), m.weight, "bf16_1x1")
+                if ks == 1 and bf16 and K.conv1x1_bf16_supported(cout, cin, hw_any):
+                    add(bf_maps, self._bf, c1_map(off, cout, cin, True), m.weight, "bf16_1x1_t")
                 if ks == 3 and bf16:
-                    def inst_b(view, m=m, wkey=wkey):
-                        AG._bf16_packs[wkey + (False,)] = (K.weight_key(m.weight), view, m.weight)
-                    add(bf_maps, self._bf, bf16_map(off, cout, cin, False), inst_b)
+                    add(bf_maps, self._bf, bf16_map(off, cout, cin, False), m.weight, "bf16_3x3")
                     if cin % 32 == 0:
-                        def inst_bt(view, m=m, wkey=wkey):
-                            AG._bf16_packs[wkey + (True,)] = (K.weight_key(m.weight), view, m.weight)
-                        add(bf_maps, self._bf, bf16_map(off, cout, cin, True), inst_bt)
-                if direct_fwd:
-                    def inst_d(view, m=m):
-                        m._pk, m._pkv = view, K.weight_key(m.weight)
-                    add_f32(K.conv2d_pack_weight(bits(idx_like(m.weight))), inst_d)
+                        add(bf_maps, self._bf, bf16_map(off, cout, cin, True), m.weight, "bf16_3x3_t")
                 if ks == 1:
+                    add_f32(K.conv2d_pack_weight(bits(idx_like(m.weight))), m.weight, "direct")
                     wt = bits(idx_like(m.weight).transpose(0, 1).flip(2, 3))
-
-                    def inst_dt(view, m=m, wkey=wkey):
-                        AG._dgrad_direct[wkey] = (K.weight_key(m.weight),
-                                                  dict(packed=view, wt=m.weight.detach().transpose(0, 1)))
-                    add_f32(K.conv2d_pack_weight(wt), inst_dt)
+                    add_f32(K.conv2d_pack_weight(wt), m.weight, "dgrad")
         self.f32_map = torch.cat(f32_maps) if f32_maps else None
         self.bf_map = torch.cat(bf_maps) if bf_maps else None
         self.f32_dst = torch.empty(self.f32_map.numel(), dtype=torch.float32, device=dev) if f32_maps else None
@@ -199,14 +174,15 @@ class PackPlan:
         self.run()
 
     def run(self):
-        if self.f32_map is not None:
-            K.gather_pack(self.flat.data, self.f32_map, self.f32_dst)
-            for off, n, install in self._f32:
-                install(self.f32_dst[off:off + n])
-        if self.bf_map is not None:
-            K.gather_pack(self.flat.data, self.bf_map, self.bf_dst)
-            for off, n, install in self._bf:
-                install(self.bf_dst[off:off + n])
+        for gather_map, dst, sinks in ((self.f32_map, self.f32_dst, self._f32), (self.bf_map, self.bf_dst, self._bf)):
+            if gather_map is None:
+                continue
+            K.gather_pack(self.flat.data, gather_map, dst)
+            for off, n, weight, kind in sinks:
+                view = dst[off:off + n]
+                if kind == "dgrad":                         # the form autograd._dgrad_pack builds for a 1x1 layer
+                    view = dict(packed=view, wt=weight.detach().transpose(0, 1))
+                weight_images.install(weight, kind, view)
 
 
 def annealing_cos(start, end, pct):

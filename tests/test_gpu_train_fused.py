@@ -201,12 +201,13 @@ def test_pack_plan_matches_individual_packs(dev):
     """sassd.train.PackPlan: after an optimizer step every cached weight image (sparse fwd / transposed, direct conv fwd
     / data-gradient, bf16 fwd / data-gradient) equals what the individual pack routine produces from the new weights."""
     import os
-    from sassd import autograd as AG, spconv as SP, train
+    from sassd import autograd as AG, spconv as SP, train, weight_images as WI
     from sassd.detector import _HipConv2d, build_detector
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cfg = Config.fromfile(os.path.join(root, "configs", "car_cfg.py"))
     try:
         AG.set_bev_precision("bf16")
+        WI.store.clear()
         model = synth.randomize_detector(build_detector(cfg.model, cfg.train_cfg, cfg.test_cfg), 0).to(dev)
         opt = train.build_optimizer(model, cfg.optimizer, 1)
         assert opt.pack_plan is not None
@@ -219,47 +220,50 @@ def test_pack_plan_matches_individual_packs(dev):
             if isinstance(m, SP.SparseConvolution):
                 k = int(np.prod(m.kernel_size))
                 w = m.weight.detach().reshape(k, m.in_channels, m.out_channels).contiguous()
-                assert m._packed_version == K.weight_key(m.weight)
-                assert torch.equal(m._packed, K.spconv_pack_weight(w)); checked["sp"] += 1
+                assert torch.equal(WI.peek(m.weight, "spconv"), K.spconv_pack_weight(w)); checked["sp"] += 1
+                assert m.packed_weight() is WI.peek(m.weight, "spconv")
                 if m.in_channels >= 16:
                     # submanifold layers differentiate on the forward rulebook: offset-reversed transposed image
                     rev = isinstance(m, SP.SubMConv3d) and k == 27 and AG.SparseConvFn.subm_on_forward_table
-                    gen, pk, src = AG._sp_t_packs[(m.weight.data_ptr(), (k, m.in_channels, m.out_channels)) + ((True,) if rev else ())]
+                    kind = "spconv_t_rev" if rev else "spconv_t"
                     ref = K.spconv_pack_weight_t(w.flip(0).contiguous() if rev else w)
-                    assert gen == K.weight_key(m.weight) and torch.equal(pk, ref); checked["spt"] += 1
-                    assert src is m.weight                   # (the entry pins the tensor it was packed from)
+                    assert torch.equal(WI.peek(m.weight, kind), ref); checked["spt"] += 1
+                    assert WI.pinned(m.weight, kind) is m.weight          # (the entry pins the tensor it was packed from)
+                    assert AG._spconv_t_pack(m.weight.view(k, m.in_channels, m.out_channels), rev) is WI.peek(m.weight, kind)
             elif isinstance(m, _HipConv2d):
                 w = m.weight.detach()
-                key = (w.data_ptr(), tuple(w.shape))
                 if m.kernel_size[0] == 1:
-                    assert m._pkv == K.weight_key(m.weight) and torch.equal(m._pk, K.conv2d_pack_weight(w.contiguous()))
-                    gen, d = AG._dgrad_direct[key]
+                    assert torch.equal(WI.peek(m.weight, "direct"), K.conv2d_pack_weight(w.contiguous()))
+                    assert m.packed_weight() is WI.peek(m.weight, "direct")
+                    d = WI.peek(m.weight, "dgrad")
                     wt = w.transpose(0, 1).flip(2, 3).contiguous()
-                    assert gen == K.weight_key(m.weight) and torch.equal(d["packed"], K.conv2d_pack_weight(wt))
+                    assert torch.equal(d["packed"], K.conv2d_pack_weight(wt))
                     assert tuple(d["wt"].shape) == tuple(wt.shape)
+                    assert AG._dgrad_pack(m.weight, 200, 176) is d           # (a 1x1 layer's image does not depend on the map size)
                     checked["direct"] += 1; checked["dgrad"] += 1
                     for tr, name in ((False, "c1"), (True, "c1t")):                 # (round 6) bf16 MFMA fragments of the 1x1 convs
                         co_g, ci_g = (m.in_channels, m.out_channels) if tr else (m.out_channels, m.in_channels)
                         if K.conv1x1_bf16_supported(ci_g, co_g, 4):
-                            gen, pk, src = AG._bf16_1x1_packs[key + (tr,)]
-                            assert src is m.weight and gen == K.weight_key(m.weight)
-                            assert torch.equal(pk, K.conv1x1_bf16_pack_weight(w, tr)); checked[name] += 1
+                            kind = "bf16_1x1_t" if tr else "bf16_1x1"
+                            assert WI.pinned(m.weight, kind) is m.weight
+                            assert torch.equal(WI.peek(m.weight, kind), K.conv1x1_bf16_pack_weight(w, tr)); checked[name] += 1
                 else:
-                    gen, pk, src = AG._bf16_packs[key + (False,)]
-                    assert src is m.weight
+                    assert WI.pinned(m.weight, "bf16_3x3") is m.weight
                     wp = w                                              # (round 6) Cout zero-padded to a multiple of 32: 28 -> 32
                     if m.out_channels % 32:
                         wp = torch.cat([w, w.new_zeros((AG.bf16_cout_pad(m.out_channels) - m.out_channels,) + tuple(w.shape[1:]))], 0)
-                    assert gen == K.weight_key(m.weight) and torch.equal(pk, K.conv2d_bf16_pack_weight(wp.contiguous()))
+                    assert torch.equal(WI.peek(m.weight, "bf16_3x3"), K.conv2d_bf16_pack_weight(wp.contiguous()))
                     checked["bf"] += 1
                     if m.in_channels % 32 == 0:
-                        gen, pk, src = AG._bf16_packs[key + (True,)]
-                        assert src is m.weight
+                        assert WI.pinned(m.weight, "bf16_3x3_t") is m.weight
                         wt = w.transpose(0, 1).flip(2, 3).contiguous()
-                        assert gen == K.weight_key(m.weight) and torch.equal(pk, K.conv2d_bf16_pack_weight(wt))
+                        assert torch.equal(WI.peek(m.weight, "bf16_3x3_t"), K.conv2d_bf16_pack_weight(wt))
                         checked["bft"] += 1
         assert checked["sp"] >= 14 and checked["spt"] >= 13 and checked["bf"] == 8 and checked["bft"] == 8, checked
         assert checked["direct"] >= 5 and checked["dgrad"] >= 5 and checked["c1"] >= 5 and checked["c1t"] >= 5, checked
+        # the one bound covers what four bounded caches, a plain dict and the module attributes held: a detector with its
+        # PackPlan must leave more than half of it to lazily built images and transient keys
+        assert sum(checked.values()) <= len(WI.store) < WI.store.MAX // 2, (checked, len(WI.store))
     finally:
         AG.set_bev_precision("fp32")
 

@@ -2,9 +2,9 @@
 unbind instead of slice / divide / multiply per term), the pinned packed-weight cache, the cached batch constants."""
 import torch
 
-from sassd import autograd as AG
 from sassd import detector as D
 from sassd import train as T
+from sassd import weight_images as WI
 
 
 def test_scaled_terms_equal_the_per_term_formulation():
@@ -30,32 +30,34 @@ def test_scaled_terms_equal_the_per_term_formulation():
 
 
 def test_pack_cache_pins_its_source_and_stays_bounded():
-    c = AG._PackCache()
-    keep = []
-    for i in range(c.MAX + 10):
-        src = torch.zeros(4)
-        c.put(("k", i), ("gen", i), torch.full((2,), float(i)), src)
-        keep.append(src.data_ptr())
+    c = WI.ImageStore()
+    srcs = [torch.zeros(4) for _ in range(c.MAX + 10)]
+    for i, src in enumerate(srcs):
+        c.install(src, "k", torch.full((2,), float(i)))
     assert len(c) <= c.MAX
-    gen, pack, src = c[("k", c.MAX + 9)]
-    assert gen == ("gen", c.MAX + 9) and float(pack[0]) == c.MAX + 9 and src.data_ptr() == keep[-1]
-    assert ("k", 0) not in c                               # the oldest entries were dropped (a dropped entry = a re-pack)
+    last = srcs[-1]
+    assert float(c.peek(last, "k")[0]) == c.MAX + 9 and c.pinned(last, "k") is last
+    assert c.peek(srcs[0], "k") is None                    # the oldest entries were dropped (a dropped entry = a re-pack)
     # while an entry lives its source tensor lives: no other tensor can be handed that address
-    live = {v[2].data_ptr() for v in c.values()}
+    live = {c.pinned(t, "k").data_ptr() for t in srcs if c.peek(t, "k") is not None}
+    assert len(live) == len(c) == c.MAX
+    del srcs, src
     fresh = [torch.zeros(4) for _ in range(64)]
     assert not (live & {t.data_ptr() for t in fresh})
     # overwriting a key does not grow the cache
     n = len(c)
-    c.put(("k", c.MAX + 9), ("gen", "new"), torch.zeros(1), torch.zeros(1))
-    assert len(c) == n and c[("k", c.MAX + 9)][0] == ("gen", "new")
+    new = torch.zeros(1)
+    c.install(last, "k", new)
+    assert len(c) == n and c.peek(last, "k") is new
     # least recently USED goes first: a long-lived entry that keeps being hit survives any number of transient keys
-    c2 = AG._PackCache()
-    c2.put("param", 0, torch.zeros(1), torch.zeros(1))
-    for i in range(3 * c2.MAX):
-        assert c2.get("param") is not None
-        c2.put(("transient", i), 0, torch.zeros(1), torch.zeros(1))
-    assert "param" in c2 and len(c2) <= c2.MAX and ("transient", 0) not in c2
-    assert c2.get("missing") is None
+    c2 = WI.ImageStore()
+    param, transient = torch.zeros(1), [torch.zeros(1) for _ in range(3 * c2.MAX)]
+    c2.install(param, "param", torch.zeros(1))
+    for t in transient:
+        assert c2.peek(param, "param") is not None
+        c2.install(t, "transient", torch.zeros(1))
+    assert c2.peek(param, "param") is not None and len(c2) <= c2.MAX and c2.peek(transient[0], "transient") is None
+    assert c2.peek(torch.zeros(1), "missing") is None
 
 
 def test_cached_batch_constants():
