@@ -501,6 +501,36 @@ int sassd_rescore_nms(const float *guided, const float *logits, const int32_t *l
                       int capD, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Frame record: the LAST node of a captured frame.  sassd_frame_seal copies the detection buffers sassd_rescore_nms
+ * left behind into ONE fixed-size, self-describing device record, so that a frame leaves the GPU in one asynchronous
+ * copy (sassd.stream.FrameStream; the reference reads its detections with three blocking copies per sample,
+ * ssd_rotate_head.py:529-531).  One kernel launch, grid sized by batch * capD, plain loads and vector stores: no
+ * atomics, no memset -- a frame that ends in it still holds kernel nodes only.  It READS boxes / scores / labels /
+ * counts, the word at `seq` and the word at `status`, and writes nothing but `record`.
+ *
+ * CONTRACT -- the record, in 32-bit little-endian words (sassd.stream.record_layout returns the same byte offsets):
+ *   word 0            magic/version  SASSD_FRAME_MAGIC
+ *   word 1            seq            the int32 at `seq` when the kernel ran (a captured graph bakes its kernel
+ *                                    arguments, so the sequence number is staged in device memory with the inputs)
+ *   word 2            status         the int32 at `status` (SASSD_ST_* bits) at the end of this frame
+ *   word 3            B              batch
+ *   word 4            capD
+ *   words 5 .. 5+B-1  counts[B]      counts[b] clamped to 0 .. capD
+ *   (zero words up to H = SASSD_FRAME_HEADER_WORDS(B) = 5 + B rounded up to a multiple of 4: the body is 16-byte
+ *    aligned in a 16-byte aligned record)
+ *   words H ..        boxes  [B][capD][7] f32, then scores [B][capD] f32, then labels [B][capD] i32
+ * Every row at or past counts[b] is written as zero words, so the record is a pure function of the frame: two runs of
+ * the same frame give the same bytes.  sassd_frame_record_bytes = 4 * (H + 9 * B * capD), 0 for an impossible shape.
+ * `record` must be 4-byte aligned and record_bytes at least that size (SASSD_ENOSPC otherwise).
+ * ---------------------------------------------------------------------------------------------- */
+#define SASSD_FRAME_MAGIC 0x53460001                       /* 'S' 'F', layout version 1 */
+#define SASSD_FRAME_HEADER_WORDS(B) ((5 + (B) + 3) / 4 * 4)
+size_t sassd_frame_record_bytes(int batch, int capD);
+int sassd_frame_seal(const float *boxes, const float *scores, const int32_t *labels, const int32_t *counts,
+                     int batch, int capD, const int32_t *seq, const int32_t *status, void *record,
+                     size_t record_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * iou3d_cuda operator surface (mmdet/ops/iou3d/src/iou3d.cpp:31,52,73; kernels iou3d_kernel.cu:223-292).
  * boxes (x1,y1,x2,y2,ry) f32.  nms: boxes sorted by descending score; keep [n] i64 and num_keep are DEVICE
  * buffers (the reference fills a CPU LongTensor after a blocking D2H of the mask, iou3d.cpp:92-94).

@@ -82,6 +82,9 @@ _SIGS = {
     "sassd_pswarp_sample_bwd": (_I, [_P, _I, _I, _I, _P, _P, _I, _F, _F, _F, _P, _P, _P, _P]),
     "sassd_rescore_nms_workspace_bytes": (_SZ, [_I, _I]),
     "sassd_rescore_nms": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _P, _I, _P, _P, _SZ, _P]),
+    # frame record (include/sassd.h "Frame record"; sassd.stream)
+    "sassd_frame_record_bytes": (_SZ, [_I, _I]),
+    "sassd_frame_seal": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _SZ, _P]),
     "sassd_boxes_overlap_bev": (_I, [_P, _I, _P, _I, _P, _P]),
     "sassd_boxes_iou_bev": (_I, [_P, _I, _P, _I, _P, _P]),
     "sassd_nms_workspace_bytes": (_SZ, [_I]),

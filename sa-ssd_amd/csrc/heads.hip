@@ -747,6 +747,75 @@ extern "C" int sassd_rescore_nms(const float *guided, const float *logits, const
     return sassd_launch_status();
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Frame record (include/sassd.h "Frame record"): header + boxes + scores + labels of one frame in one buffer.  One thread
+// per detection row: element i + k * N of the flat box array for k = 0..6 (coalesced), score i, label i; the first H threads
+// also write the header words.  Rows at or past their sample's count become zero words.
+// ------------------------------------------------------------------------------------------------------------------
+struct SealParams {
+    const float *boxes; const float *scores; const int32_t *labels; const int32_t *counts;
+    const int32_t *seq; const int32_t *status;
+    int32_t *rec;
+    int B, capD, hdr;
+};
+
+__device__ __forceinline__ int seal_count(const SealParams &P, int b)
+{
+    const int c = P.counts[b];
+    return c < 0 ? 0 : (c > P.capD ? P.capD : c);
+}
+
+__global__ void __launch_bounds__(256) frame_seal_kernel(SealParams P)
+{
+    const int N = P.B * P.capD;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < P.hdr) {
+        int v = 0;
+        if (i == 0) v = SASSD_FRAME_MAGIC;
+        else if (i == 1) v = P.seq[0];
+        else if (i == 2) v = P.status[0];
+        else if (i == 3) v = P.B;
+        else if (i == 4) v = P.capD;
+        else if (i < 5 + P.B) v = seal_count(P, i - 5);
+        P.rec[i] = v;
+    }
+    if (i >= N) return;
+    float *rb = (float *)(P.rec + P.hdr);
+    float *rs = rb + (size_t)7 * N;
+    int32_t *rl = (int32_t *)(rs + N);
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        const int e = i + k * N, row = e / 7, b = row / P.capD;
+        rb[e] = (row - b * P.capD) < seal_count(P, b) ? P.boxes[e] : 0.f;
+    }
+    const int b = i / P.capD;
+    const bool live = (i - b * P.capD) < seal_count(P, b);
+    rs[i] = live ? P.scores[i] : 0.f;
+    rl[i] = live ? P.labels[i] : 0;
+}
+
+extern "C" size_t sassd_frame_record_bytes(int batch, int capD)
+{
+    if (batch < 1 || capD < 1 || (long)batch * capD > (1L << 24)) return 0;
+    return 4 * ((size_t)SASSD_FRAME_HEADER_WORDS(batch) + (size_t)9 * batch * capD);
+}
+
+extern "C" int sassd_frame_seal(const float *boxes, const float *scores, const int32_t *labels, const int32_t *counts,
+                                int batch, int capD, const int32_t *seq, const int32_t *status, void *record,
+                                size_t record_bytes, void *stream_)
+{
+    if (!boxes || !scores || !labels || !counts || !seq || !status || !record) return SASSD_EINVAL;
+    const size_t need = sassd_frame_record_bytes(batch, capD);
+    if (need == 0 || ((uintptr_t)record & 3)) return SASSD_EINVAL;
+    if (record_bytes < need) return SASSD_ENOSPC;
+    SealParams P;
+    P.boxes = boxes; P.scores = scores; P.labels = labels; P.counts = counts; P.seq = seq; P.status = status;
+    P.rec = (int32_t *)record; P.B = batch; P.capD = capD; P.hdr = SASSD_FRAME_HEADER_WORDS(batch);
+    const int threads = batch * capD > P.hdr ? batch * capD : P.hdr;
+    hipLaunchKernelGGL(frame_seal_kernel, dim3(cdiv(threads, 256)), dim3(256), 0, (hipStream_t)stream_, P);
+    return sassd_launch_status();
+}
+
 extern "C" int sassd_boxes_overlap_bev(const float *boxes_a, int num_a, const float *boxes_b, int num_b,
                                        float *ans_overlap, void *stream_)
 {

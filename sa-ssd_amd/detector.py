@@ -964,13 +964,36 @@ class SingleStageDetector(nn.Module):
                          anchors_src=src[0] if isinstance(src, (list, tuple)) and len(src) else None)
         vx = self.backbone(ret['voxels'], ret['num_points'])
         plan.run_from_voxels(vx, ret['coordinates'], ret['anchors_mask'])
+        return self.result_annos(plan.results(), img_meta)
+
+    def result_annos(self, results, img_meta):
+        """Per-sample detections (boxes, scores, labels) as InferencePlan.results() / FrameStream.collect() return them ->
+        what forward_test returns for these img_meta (its docstring)."""
         out = []
-        for (boxes, scores, labels), meta in zip(plan.results(), img_meta):
+        for (boxes, scores, labels), meta in zip(results, img_meta):
             if isinstance(meta, dict) and meta.get('calib') is not None:
                 out.append(kitti_bbox2results(boxes, scores, labels, meta, class_names=self.class_names))
             else:
                 out.append(dict(boxes_lidar=boxes, scores=scores, labels=labels))
         return out
+
+    def frame_stream(self, anchors, inflight=3, points_cap=None, batch_size=1, device=None, **kw):
+        """A sassd.stream.FrameStream over this model's weights: raw point clouds in, `inflight` frames in flight, the
+        detections of plan.results() out, in order.  Thresholds and precisions come from test_cfg the way plan() takes them
+        (score_thr, nms.iou_thr; precision / sparse_precision unless given); the voxelizer's settings and anything else
+        InferencePlan accepts go through **kw.  The stream holds a copy of the weights as they are now."""
+        from .stream import FrameStream
+        precision = kw.pop('precision', None) or ((self.test_cfg or {}).get('precision') or 'fp32')
+        sparse_precision = kw.pop('sparse_precision', None) or ((self.test_cfg or {}).get('sparse_precision') or 'fp32')
+        tc = self.test_cfg.get('extra', self.test_cfg) if self.test_cfg else {}
+        kw.setdefault('score_thr', tc.get('score_thr', 0.3))
+        kw.setdefault('iou_thr', tc.get('nms', {}).get('iou_thr', 0.1))
+        if device is None:
+            device = next(self.parameters()).device
+        an = anchors.detach().cpu().numpy() if torch.is_tensor(anchors) else np.asarray(anchors)
+        return FrameStream(self.state_dict(), inflight=inflight, points_cap=points_cap, batch_size=batch_size,
+                           anchors=an.reshape(-1, 7), device=device, precision=precision, sparse_precision=sparse_precision,
+                           **dict(self._cfg, **kw))
 
     def forward(self, img, img_meta, return_loss=True, **kwargs):
         if return_loss:

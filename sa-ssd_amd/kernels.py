@@ -904,6 +904,29 @@ def rescore_nms(guided, logits, labels, counts, score_thr, iou_thr, cap_d, out=N
     return dict(boxes=boxes, scores=scores, labels=olabels, counts=ocounts)
 
 
+def frame_record_bytes(batch, cap_d):
+    """Size of the frame record of include/sassd.h ("Frame record") for `batch` samples of `cap_d` detection rows."""
+    n = int(_C.lib().sassd_frame_record_bytes(int(batch), int(cap_d)))
+    if n == 0:
+        raise ValueError("no frame record for batch %d x capD %d" % (batch, cap_d))
+    return n
+
+
+def frame_seal(det, seq, status, record=None):
+    """The detection buffers `det` (rescore_nms's out dict), the int32 words at `seq` and `status` -> one frame record
+    (uint8 tensor of frame_record_bytes).  Reads its inputs, writes the record only; one kernel launch."""
+    boxes, scores, labels, counts = det["boxes"], det["scores"], det["labels"], det["counts"]
+    _chk_cuda(boxes, scores, labels, counts, seq, status, record)
+    b, cap_d = int(boxes.shape[0]), int(boxes.shape[1])
+    nbytes = frame_record_bytes(b, cap_d)
+    if record is None:
+        record = torch.empty(nbytes, dtype=torch.uint8, device=boxes.device)
+    rc = _C.lib().sassd_frame_seal(_C.ptr(boxes), _C.ptr(scores), _C.ptr(labels), _C.ptr(counts), b, cap_d, _C.ptr(seq),
+                                   _C.ptr(status), _C.ptr(record), record.numel() * record.element_size(), _C.stream())
+    _C.check(rc, "sassd_frame_seal")
+    return record
+
+
 # --------------------------------------------------------------------------------------------------
 def boxes_overlap_bev(a, b, out=None):
     _chk_cuda(a, b)

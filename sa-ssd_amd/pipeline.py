@@ -204,6 +204,7 @@ class InferencePlan:
         # per-call kernel-selection words of the C ABI (None: the binding's default, 0 in production)
         self.spconv_cfg, self.wino4_cfg = spconv_cfg, wino4_cfg
         self.graph = None
+        self.record = None         # device frame record: capture(seal=True)
         self._wsid = id(self)
         # coordinate-only work (rulebooks, anchors_mask) runs on a side stream, overlapping the feature path
         self.overlap = bool(overlap)
@@ -597,14 +598,24 @@ class InferencePlan:
             return self._tail(anchors_mask)
 
     # ---- hipGraph: the whole frame as ONE launch ---------------------------------------------------------
-    def capture(self, points_cap, ndim=4, stages=("voxelize", "backbone", "tail")):
+    def capture(self, points_cap, ndim=4, stages=("voxelize", "backbone", "tail"), seal=False):
         """Capture the frame (raw points -> detections, side stream included) into a hipGraph.  Input staging:
         `self.pts_in[b]` [points_cap, ndim] f32 and `self.npts` int32 [B]; `run_graph(clouds)` fills them and replays.
-        `stages` lets a caller capture a sub-range (e.g. only the sparse backbone for a roofline measurement)."""
+        `stages` lets a caller capture a sub-range (e.g. only the sparse backbone for a roofline measurement).
+        seal=True: the frame's last node is sassd_frame_seal -- `self.record` (device uint8) then holds the frame record of
+        include/sassd.h after every replay, its `seq` word echoed from a device word, which shares one int32 block
+        [seq, npts[B]] with `self.npts` so that both are staged in one copy (sassd.stream.FrameStream).
+        The launch sequence that was captured stays on the plan as `_frame_fn`, for inspection only (a test captures it once
+        more into a plain hipGraph to count its node types); nothing on the frame path calls it."""
         dev = self.dev
         self.pts_cap = int(points_cap)
         self.pts_in = [torch.zeros(self.pts_cap, ndim, dtype=torch.float32, device=dev) for _ in range(self.B)]
-        self.npts = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        if seal:
+            self._stage_words = torch.zeros(1 + self.B, dtype=torch.int32, device=dev)
+            self._seq, self.npts = self._stage_words[:1], self._stage_words[1:]
+            self.record = torch.zeros(K.frame_record_bytes(self.B, self.capD), dtype=torch.uint8, device=dev)
+        else:
+            self.npts = torch.zeros(self.B, dtype=torch.int32, device=dev)
         assert self.prof is None, "per-stage event timing and graph capture exclude each other"
 
         def frame():
@@ -623,6 +634,8 @@ class InferencePlan:
                     self._tail(None)
                 elif self.overlap:
                     torch.cuda.current_stream(self.dev).wait_event(self.mask_ev)      # join the side stream
+                if seal:
+                    K.frame_seal(self.det, self._seq, self.status, self.record)
 
         # capture needs a non-default stream (the legacy null stream cannot be captured)
         cap = torch.cuda.Stream(device=dev)
@@ -631,6 +644,7 @@ class InferencePlan:
             frame()                               # warm-up: every workspace / lazily created event exists
             cap.synchronize()
             self.graph = K.Graph().capture(frame)
+        self._frame_fn = frame                     # the captured launch sequence (tools / tests capture it again to inspect it)
         # the graph holds raw pointers into this plan's grow-only kernel workspaces: keep the tensors it was captured
         # with alive, so that a later eager call that regrows a workspace cannot free memory the graph still replays on
         self._graph_ws = K.scoped_workspaces(self._wsid)

@@ -7,6 +7,7 @@ reference walks the val split serially on one GPU; here `single_test` takes this
 (no data-path collective) and the per-frame result annotations are gathered on the host in dataset order."""
 import glob
 import os
+from collections import deque
 
 import torch
 
@@ -57,9 +58,13 @@ def train_model(model, optimizer, train_loader, lr_scheduler, sync, start_epoch,
     return it
 
 
-def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=None, world=None):
+def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=None, world=None, inflight=0,
+                points_cap=None):
     """Run the detector over `dataset` (test mode) -> list of KITTI result annotations in dataset order on every rank
-    (this rank's frames are computed here, the others' gathered from their ranks).  `saveto`: also write result files."""
+    (this rank's frames are computed here, the others' gathered from their ranks).  `saveto`: also write result files.
+    inflight > 0: the frames' raw points go through model.frame_stream(...) with that many frames in flight (1..4) instead of
+    collate + model(...): same annotations, the voxelizer and the anchor mask inside the captured frame.  `points_cap`: the
+    largest cloud of the stream (default: from the sizes of this rank's point files)."""
     if rank is None or world is None:
         rank, _, world = D.env_world() if D.dist.is_initialized() else (0, 0, 1)
     if class_names is not None:
@@ -68,8 +73,11 @@ def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=N
     mine = D.frame_shard(len(dataset), rank, world)
     annos = []
     with torch.no_grad():
-        for batch in FrameLoader(dataset, 1, sampler=mine, num_workers=workers):
-            annos += model(**batch)
+        if inflight:
+            annos = _stream_test(model, dataset, mine, workers, inflight, points_cap)
+        else:
+            for batch in FrameLoader(dataset, 1, sampler=mine, num_workers=workers):
+                annos += model(**batch)
     merged = [None] * len(dataset)
     for part_rank, part in enumerate(D.gather_results(annos) if world > 1 else [annos]):
         for idx, anno in zip(D.frame_shard(len(dataset), part_rank, world), part):
@@ -77,6 +85,46 @@ def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=N
     if saveto is not None and rank == 0:
         kitti.write_label_annos(merged, saveto)
     return merged
+
+
+def _stream_test(model, dataset, indices, workers, inflight, points_cap=None):
+    """single_test's frames through a FrameStream: the point files are read ahead on `workers` threads, submitted as host
+    clouds, and every result becomes the annotation forward_test builds for the frame's img_meta."""
+    from concurrent.futures import ThreadPoolExecutor
+    if not dataset.with_point:
+        raise ValueError("single_test(inflight > 0) feeds raw points: the dataset needs with_point=True")
+    indices = [int(i) for i in indices]
+    if not indices:
+        return []
+    if points_cap is None:                      # the files load_frame reads: [N, 4] float32 (kitti_common.read_lidar)
+        sizes = [os.path.getsize(os.path.join(dataset.lidar_prefix, '%06d.bin' % dataset.sample_ids[i])) for i in indices]
+        if any(n % 16 for n in sizes):
+            raise ValueError("a point file under %s is not a whole number of 16-byte points: pass points_cap" % dataset.lidar_prefix)
+        points_cap = (max(sizes) // 16 + 1023) // 1024 * 1024 or 1024      # rounded up to 1024 points
+    gen = dataset.generator
+    fs = model.frame_stream(dataset.anchors, inflight=inflight, points_cap=points_cap, batch_size=1, device=dataset._dev(),
+                            anchors_bv=dataset.anchors_bv, voxel_size=tuple(gen.voxel_size),
+                            point_cloud_range=tuple(gen.point_cloud_range), max_num_points=gen.max_num_points_per_voxel,
+                            max_voxels=gen._max_voxels, anchor_area_threshold=dataset.anchor_area_threshold)
+    metas, annos = deque(), []
+    try:
+        with ThreadPoolExecutor(max(1, int(workers))) as pool:
+            def batches():
+                ahead = max(1, int(workers)) + inflight
+                pending = deque(pool.submit(dataset.load_frame, i, False) for i in indices[:ahead])
+                nxt = len(pending)
+                while pending:
+                    fr = pending.popleft().result()
+                    if nxt < len(indices):
+                        pending.append(pool.submit(dataset.load_frame, indices[nxt], False))
+                        nxt += 1
+                    metas.append(dict(img_shape=fr['img_shape'], sample_idx=fr['sample_idx'], calib=fr['calib']))
+                    yield [fr['points']]
+            for _, dets in fs.map(batches()):
+                annos += model.result_annos(dets, [metas.popleft()])
+    finally:
+        fs.close()
+    return annos
 
 
 def evaluate(dataset, outputs, class_names=None):
