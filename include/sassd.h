@@ -314,10 +314,33 @@ int sassd_conv2d_wino4_chain_tail(const float *prev_scale, const float *prev_shi
  * were densified.  A chain call with `tile_map` (src_products == 0) transforms and multiplies the active tiles only
  * (compacted columns); the NEXT chain call passes the same map as `prev_tile_map` (or this call, with y != NULL, its own):
  * an inactive tile's products are exactly zero, so the result is bit-identical to the dense launch.  NULL = all tiles.
- * tile_map: sassd_wino4_tile_map_ints(batch, H, W) int32 (0 = unsupported: more than 65536 tiles). */
+ * tile_map: sassd_wino4_tile_map_ints(batch, H, W) int32, 16-byte aligned like `indices` (0 = unsupported: more than 2^24
+ * tiles): [0] active tiles, [1] tiles, [2..3] 0, tpos[T] (column of tile t or -1), tlist[T] (tile of column j, ascending), then
+ * the call's own tile flags.  Two grid-wide launches behind one fill kernel. */
 size_t sassd_wino4_tile_map_ints(int batch, int H, int W);
 int sassd_wino4_tile_map(const int32_t *indices, const int32_t *n_ptr, int cap, int batch, int H, int W,
                          int32_t *tile_map, void *stream);
+
+/* BEVNet conv0 straight from the sparse tensor: the first layer of a chain WITHOUT the dense [B, C D, H, W] map in between.
+ *   sassd_wino4_sparse_prepare   per frame, from the level-3 coordinates alone (indices [cap,4] (b, z, y, x), rows past
+ *                                min(*n_ptr, cap) ignored, rows unique per coordinate): the tile map above AND the pixel -> row
+ *                                index grid, int32 [B][D][H][W] (sassd_wino4_sparse_grid_ints, -1 = empty), cleared by a fill
+ *                                kernel and filled one thread per row -- no memset node, no atomics.
+ *   sassd_conv2d_wino4_chain_sparse   = sassd_densify(channel_order 1) + sassd_conv2d_wino4_chain(x, src_products 0, tile_map)
+ *                                bit for bit: the input transform gathers feats [rows, C] (fp32, 16-byte aligned rows: C % 4 == 0)
+ *                                through the grid into V[p][d C + c][column of the tile], then the same 36 GEMMs on the active
+ *                                columns and, with y != NULL, the same output transform; y == NULL leaves the products for the
+ *                                next sassd_conv2d_wino4_chain call (prev_tile_map = this tile_map).
+ * SASSD_EINVAL before any launch: C * D != Cin, Cin % 32 != 0, D > 8 (documented precondition of the grid), C % 4 != 0, no
+ * tile_map, a shape sassd_conv2d_wino4_supported refuses, a pointer that is not 16-byte aligned; SASSD_ENOSPC: workspace below
+ * sassd_conv2d_wino4_chain_workspace_bytes(batch, cmax, H, W). */
+size_t sassd_wino4_sparse_grid_ints(int batch, int D, int H, int W);
+int sassd_wino4_sparse_prepare(const int32_t *indices, const int32_t *n_ptr, int cap, int batch, int D, int H, int W,
+                               int32_t *grid, int32_t *tile_map, void *stream);
+int sassd_conv2d_wino4_chain_sparse(const float *feats, int C, int D, const int32_t *grid, const float *w_packed,
+                                    const float *scale, const float *shift, int relu, float *y, int batch, int Cin, int Cout,
+                                    int cmax, int H, int W, const int32_t *tile_map, int cfg, void *workspace,
+                                    size_t workspace_bytes, void *stream);
 
 /* 1x1 convolution with >= 128 output channels (BEVNet conv7, cmn.py:262) as a plain fp32-MFMA GEMM over the NCHW
  * tensor (y[b] [Cout x HW] = W [Cout x Cin] . x[b] [Cin x HW]) with the folded BatchNorm / bias / ReLU epilogue; the

@@ -171,6 +171,9 @@ _SIGS = {
     "sassd_conv2d_wino4_chain_tail": (_I, [_P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _SZ, _P]),
     "sassd_wino4_tile_map_ints": (_SZ, [_I, _I, _I]),
     "sassd_wino4_tile_map": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "sassd_wino4_sparse_grid_ints": (_SZ, [_I, _I, _I, _I]),
+    "sassd_wino4_sparse_prepare": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "sassd_conv2d_wino4_chain_sparse": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _SZ, _P]),
     "sassd_gather_pack": (_I, [_P, _P, _P, C.c_long, _I, _P]),
     "sassd_grad_sumsq": (_I, [_P, C.c_long, _P, _P]),
     "sassd_adam_step": (_I, [_P, _P, _P, _P, C.c_long, _P, _F, _F, _F, _F, _F, _I, _F, _F, _P]),

@@ -902,41 +902,77 @@ extern "C" int sassd_conv2d_wino4_chain_tail(const float *prev_scale, const floa
 // 4x4-tile patches are occupied on a KITTI frame) -------------------------------------------------------------------------
 // A tile is active when any occupied pixel lies in its 6x6 input patch; inactive tiles have all-zero transformed input,
 // all-zero products and the output relu(shift) -- exactly what the dense launch computes for them, so skipping them is
-// bit-identical.  One workgroup: flags in LDS (benign same-value byte stores), ordered compaction by a block scan.
+// bit-identical.  Two grid-wide launches behind one fill (rounds 4-6: one workgroup did all of it, 15 us on one CU with the
+// row loop as a chain of dependent loads, and its LDS flags capped the map at 65536 tiles):
+//   1. w4_mark_kernel     one thread per sparse row: a byte flag per tile in the map's tail (benign same-value stores, no
+//                         atomics); SPARSE: also the pixel -> row index grid of the sparse input transform below
+//   2. w4_compact_kernel  ordered compaction, one tile per thread: a workgroup's base = the flags in front of its 1024 tiles
+//                         (summed again by every workgroup: T bytes at most, no grid barrier and no atomics), then a block scan
+// tpos / tlist come out in ascending tile order, as before.
 namespace {
-__global__ void __launch_bounds__(1024) w4_tile_map_kernel(const int32_t *__restrict__ idx, const int32_t *__restrict__ n_ptr,
-                                                           int cap, int B, int H, int W, int TH, int TW,
-                                                           int32_t *__restrict__ tmap)
+constexpr int kMapBlock = 1024;
+inline size_t w4_flag_off(size_t T) { return align_up(kTmapHead + 2 * T, 4); }        // ints; the flags start 16-byte aligned
+inline size_t w4_flag_ints(size_t T) { return align_up((T + 3) / 4, 4); }             // T bytes, padded to 16
+
+template <bool SPARSE>
+__global__ void __launch_bounds__(256) w4_mark_kernel(const int32_t *__restrict__ idx, const int32_t *__restrict__ n_ptr, int cap,
+                                                      int B, int D, int H, int W, int TH, int TW,
+                                                      unsigned char *__restrict__ flags, int32_t *__restrict__ grid)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char w4_flags[];
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= min(*n_ptr, cap)) return;
+    const int4 c = ((const int4 *)idx)[r];               // (b, z, y, x)
+    if (c.x < 0 || c.x >= B || c.z < 0 || c.z >= H || c.w < 0 || c.w >= W) return;
+    if (SPARSE) {
+        if (c.y < 0 || c.y >= D) return;
+        grid[(((size_t)c.x * D + c.y) * H + c.z) * W + c.w] = r;        // rows are unique per (b, z, y, x)
+    }
+    // pixel y lies in the patch rows 4 ty - 1 .. 4 ty + 4 of tile ty = y / 4, of ty - 1 when y % 4 == 0, of ty + 1 when y % 4 == 3
+    const int ty = c.z >> 2, tx = c.w >> 2;
+    const int y0 = ((c.z & 3) == 0 && ty > 0) ? ty - 1 : ty, y1 = ((c.z & 3) == 3 && ty + 1 < TH) ? ty + 1 : ty;
+    const int x0 = ((c.w & 3) == 0 && tx > 0) ? tx - 1 : tx, x1 = ((c.w & 3) == 3 && tx + 1 < TW) ? tx + 1 : tx;
+    for (int a = y0; a <= y1; ++a)
+        for (int e = x0; e <= x1; ++e) flags[(c.x * TH + a) * TW + e] = 1;
+}
+
+__global__ void __launch_bounds__(kMapBlock) w4_compact_kernel(const unsigned char *__restrict__ flags, int T,
+                                                               int32_t *__restrict__ tmap)
+{
     __shared__ int wsum[17];
-    const int T = B * TH * TW;
-    for (int i = threadIdx.x; i < (T + 3) / 4; i += 1024) ((unsigned *)w4_flags)[i] = 0u;
-    __syncthreads();
-    const int n = min(*n_ptr, cap);
-    for (int r = threadIdx.x; r < n; r += 1024) {
-        const int4 c = ((const int4 *)idx)[r];               // (b, z, y, x)
-        if (c.x < 0 || c.x >= B || c.z < 0 || c.z >= H || c.w < 0 || c.w >= W) continue;
-        // pixel y lies in the patch rows 4 ty - 1 .. 4 ty + 4 of tile ty = y / 4, of ty - 1 when y % 4 == 0, of ty + 1 when y % 4 == 3
-        const int ty = c.z >> 2, tx = c.w >> 2;
-        const int y0 = ((c.z & 3) == 0 && ty > 0) ? ty - 1 : ty, y1 = ((c.z & 3) == 3 && ty + 1 < TH) ? ty + 1 : ty;
-        const int x0 = ((c.w & 3) == 0 && tx > 0) ? tx - 1 : tx, x1 = ((c.w & 3) == 3 && tx + 1 < TW) ? tx + 1 : tx;
-        for (int a = y0; a <= y1; ++a)
-            for (int e = x0; e <= x1; ++e) w4_flags[(c.x * TH + a) * TW + e] = 1;
+    const int t0 = blockIdx.x * kMapBlock;               // (a multiple of 16: whole 16-byte words in front of this workgroup)
+    int before = 0;
+    for (int i = threadIdx.x; i < t0 / 16; i += kMapBlock) {
+        const uint4 f = ((const uint4 *)flags)[i];       // flag bytes are 0 or 1
+        before += __popc(f.x) + __popc(f.y) + __popc(f.z) + __popc(f.w);
     }
-    __syncthreads();
-    const int per = (T + 1023) / 1024;
-    const int t0 = min((int)threadIdx.x * per, T), t1 = min(t0 + per, T);
-    int cnt = 0;
-    for (int t = t0; t < t1; ++t) cnt += w4_flags[t];
+    int base;
+    block_exclusive_scan(before, wsum, &base);
+    const int t = t0 + threadIdx.x;
+    const int on = t < T ? (int)flags[t] : 0;
     int total;
-    int j = block_exclusive_scan(cnt, wsum, &total);
-    for (int t = t0; t < t1; ++t) {
-        const bool on = w4_flags[t] != 0;
+    const int j = base + block_exclusive_scan(on, wsum, &total);
+    if (t < T) {
         tmap[kTmapHead + t] = on ? j : -1;
-        if (on) tmap[kTmapHead + T + j++] = t;
+        if (on) tmap[kTmapHead + T + j] = t;
     }
-    if (threadIdx.x == 0) { tmap[0] = total; tmap[1] = T; tmap[2] = tmap[3] = 0; }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) { tmap[0] = base + total; tmap[1] = T; tmap[2] = tmap[3] = 0; }
+}
+
+template <bool SPARSE>
+int w4_build_map(const int32_t *indices, const int32_t *n_ptr, int cap, int batch, int D, int H, int W, int32_t *grid,
+                 size_t grid_bytes, int32_t *tile_map, hipStream_t stream)
+{
+    const int TH = H / 4, TW = W / 4, T = batch * TH * TW;
+    unsigned char *flags = (unsigned char *)(tile_map + w4_flag_off(T));
+    // (fill KERNELS, never memset nodes in a captured frame: DESIGN.md section 9) the grid to -1 and the flags to 0 in one launch
+    int rc = SPARSE ? sassd_fill2(grid, grid_bytes, 0xFF, flags, w4_flag_ints(T) * 4, 0, stream)
+                    : sassd_fill2(flags, w4_flag_ints(T) * 4, 0, flags, 0, 0, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(w4_mark_kernel<SPARSE>, dim3(cdiv(cap, 256)), dim3(256), 0, stream, indices, n_ptr, cap, batch, D, H, W,
+                       TH, TW, flags, grid);
+    hipLaunchKernelGGL(w4_compact_kernel, dim3(cdiv(T, kMapBlock)), dim3(kMapBlock), 0, stream, (const unsigned char *)flags, T,
+                       tile_map);
+    return sassd_launch_status();
 }
 }  // namespace
 
@@ -944,16 +980,169 @@ extern "C" size_t sassd_wino4_tile_map_ints(int batch, int H, int W)
 {
     if (batch < 1 || H < 4 || W < 4 || H % 4 || W % 4) return 0;
     const size_t T = (size_t)batch * (H / 4) * (W / 4);
-    return T <= 65536 ? kTmapHead + 2 * T : 0;               // (the flags of all tiles live in one workgroup's LDS)
+    return T <= ((size_t)1 << 24) ? w4_flag_off(T) + w4_flag_ints(T) : 0;      // head, tpos[T], tlist[T], flag bytes
 }
 
 extern "C" int sassd_wino4_tile_map(const int32_t *indices, const int32_t *n_ptr, int cap, int batch, int H, int W,
                                     int32_t *tile_map, void *stream_)
 {
     if (!indices || !n_ptr || !tile_map || cap < 1 || sassd_wino4_tile_map_ints(batch, H, W) == 0) return SASSD_EINVAL;
-    const int TH = H / 4, TW = W / 4, T = batch * TH * TW;
-    hipLaunchKernelGGL(w4_tile_map_kernel, dim3(1), dim3(1024), (size_t)align_up((size_t)T, 16), (hipStream_t)stream_, indices,
-                       n_ptr, cap, batch, H, W, TH, TW, tile_map);
+    if (((uintptr_t)tile_map & 15) || ((uintptr_t)indices & 15)) return SASSD_EINVAL;
+    return w4_build_map<false>(indices, n_ptr, cap, batch, 1, H, W, nullptr, 0, tile_map, (hipStream_t)stream_);
+}
+
+// ---- BEV conv0 straight from the sparse tensor ----------------------------------------------------------------------------
+// densify + wino4_in_kernel(tmap) moved 45 MB of zeros through HBM twice (clear the [B, C D, H, W] map, read the active tiles'
+// patches back out of it, 93 % zeros) to transport 3.4 MB of level-3 features.  Here the input transform gathers the feature
+// rows itself through a pixel -> row index grid (int32 [B][D][H][W], -1 = empty, built by w4_mark_kernel with the tile map):
+// depth-major, because one workgroup transforms ONE depth slice -- the 6 x 6 lookups of 64 neighbouring tiles are then six runs
+// of consecutive ints (a [B][H][W][8] grid costs one 128-byte line per tile and patch row for the 4 bytes that are used).
+// V[p][d C + c][j] for column j = tile tlist[j]: exactly what densify(order = 1) + wino4_in_kernel(tmap) write -- every patch value
+// is the gathered feature or 0.f, and the same bt_vec sequence (columns, then rows) runs on it.  The padding columns of the last
+// 256-column block are written as zeros (wino4_in_kernel leaves whatever its LDS held there; they only feed padding columns of M).
+namespace {
+// workgroup = 256 tile columns x one depth slice x FOUR channels: one thread = one tile, its 36 lookups shared by the four
+// channels of one 16-byte gather per occupied pixel; a tile whose patch is empty at this depth skips gathers and arithmetic
+// and stores zeros.  The 36 x 256 results of one channel go through LDS (double buffered: one barrier per channel) so that
+// every plane row leaves as 16-byte stores, as in wino4_in_kernel.  gfx950 build: 166 VGPRs (the 36 float4 of a patch stay in
+// registers across the four channels), 0 bytes of scratch, 72 KB of LDS: two workgroups per CU, 400 of them on a KITTI frame.
+__global__ void __launch_bounds__(256) wino4_in_sparse_kernel(const float *__restrict__ feats, int C, int D,
+                                                              const int32_t *__restrict__ grid, W4Geom G,
+                                                              float *__restrict__ V, const int32_t *__restrict__ tmap)
+{
+    __shared__ __attribute__((aligned(16))) float tr[2][36 * 256];
+    const int t0 = blockIdx.x * 256;
+    const int nt = tmap[0];                               // columns in use
+    if (t0 >= nt) return;                                 // (uniform)
+    const int j = t0 + threadIdx.x;
+    const int cq = C >> 2;
+    const int d = blockIdx.y / cq, c0 = (blockIdx.y - d * cq) * 4;
+    int row[6][6];
+    bool any = false;
+    if (j < nt) {
+        const int t = tmap[kTmapHead + G.T + j];
+        const int tpi = G.TH * G.TW;
+        const int b = t / tpi, r = t - b * tpi;
+        const int ty = r / G.TW, tx = r - ty * G.TW;
+        const int32_t *src = grid + ((size_t)b * D + d) * G.H * G.W;
+        const int y0 = 4 * ty - 1, x0 = 4 * tx - 1;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const int yy = y0 + i;
+            const bool rok = yy >= 0 && yy < G.H;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                const int xx = x0 + k;
+                row[i][k] = (rok && xx >= 0 && xx < G.W) ? src[(size_t)yy * G.W + xx] : -1;
+                any |= row[i][k] >= 0;
+            }
+        }
+    }
+    float4 d4[6][6];
+    if (any) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int k = 0; k < 6; ++k)
+                d4[i][k] = row[i][k] >= 0 ? *reinterpret_cast<const float4 *>(feats + (size_t)row[i][k] * C + c0)
+                                          : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    const size_t plane = (size_t)G.C * G.Tp;
+    const int c4 = threadIdx.x & 63;
+    const bool st = t0 + c4 * 4 < G.Tp;
+#pragma unroll
+    for (int ch = 0; ch < 4; ++ch) {
+        float *buf = tr[ch & 1];
+        if (any) {
+            float u[6][6];                                    // u[k] = B^T (column k of d)
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                float col[6];
+#pragma unroll
+                for (int i = 0; i < 6; ++i)
+                    col[i] = ch == 0 ? d4[i][k].x : ch == 1 ? d4[i][k].y : ch == 2 ? d4[i][k].z : d4[i][k].w;
+                float o[6];
+                bt_vec(col, o);
+#pragma unroll
+                for (int i = 0; i < 6; ++i) u[i][k] = o[i];
+            }
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                float o[6];
+                bt_vec(u[i], o);                              // (B^T d) B = rows transformed again
+#pragma unroll
+                for (int k = 0; k < 6; ++k) buf[(i * 6 + k) * 256 + threadIdx.x] = o[k];
+            }
+        } else {
+#pragma unroll
+            for (int p = 0; p < 36; ++p) buf[p * 256 + threadIdx.x] = 0.f;
+        }
+        __syncthreads();
+        // (the next channel writes the OTHER buffer; its barrier orders it behind these reads for the channel after that)
+        if (st) {
+            float *dst = V + ((size_t)d * C + c0 + ch) * G.Tp + t0 + c4 * 4;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                const int p = (threadIdx.x >> 6) + 4 * k;
+                *reinterpret_cast<float4 *>(dst + (size_t)p * plane) = *reinterpret_cast<const float4 *>(buf + p * 256 + c4 * 4);
+            }
+        }
+    }
+}
+}  // namespace
+
+extern "C" size_t sassd_wino4_sparse_grid_ints(int batch, int D, int H, int W)
+{
+    if (batch < 1 || D < 1 || D > 8 || H < 4 || W < 4 || H % 4 || W % 4) return 0;
+    return (size_t)batch * D * H * W;                     // (H and W multiples of 4: a whole number of 16-byte pieces)
+}
+
+extern "C" int sassd_wino4_sparse_prepare(const int32_t *indices, const int32_t *n_ptr, int cap, int batch, int D, int H, int W,
+                                          int32_t *grid, int32_t *tile_map, void *stream_)
+{
+    if (!indices || !n_ptr || !grid || !tile_map || cap < 1 || sassd_wino4_tile_map_ints(batch, H, W) == 0) return SASSD_EINVAL;
+    const size_t gi = sassd_wino4_sparse_grid_ints(batch, D, H, W);
+    if (gi == 0) return SASSD_EINVAL;
+    if (((uintptr_t)tile_map & 15) || ((uintptr_t)indices & 15) || ((uintptr_t)grid & 15)) return SASSD_EINVAL;
+    return w4_build_map<true>(indices, n_ptr, cap, batch, D, H, W, grid, gi * 4, tile_map, (hipStream_t)stream_);
+}
+
+extern "C" int sassd_conv2d_wino4_chain_sparse(const float *feats, int C, int D, const int32_t *grid, const float *w_packed,
+                                               const float *scale, const float *shift, int relu, float *y, int batch, int Cin,
+                                               int Cout, int cmax, int H, int W, const int32_t *tile_map, int cfg,
+                                               void *workspace, size_t workspace_bytes, void *stream_)
+{
+    const int geo = w4_geo(cfg), dbg = w4_dbg(cfg);
+    if (!feats || !grid || !tile_map || !w_packed || !workspace || batch < 1 || C < 4 || C % 4 || D < 1 || D > 8) return SASSD_EINVAL;
+    if ((long long)C * D != Cin || Cin % kKC || !sassd_conv2d_wino4_supported(Cin, Cout, H, W) || cmax < Cin || cmax < Cout)
+        return SASSD_EINVAL;
+    if (((uintptr_t)feats & 15) || ((uintptr_t)grid & 15) || ((uintptr_t)tile_map & 15) || (y && ((uintptr_t)y & 15)) ||
+        ((uintptr_t)w_packed & 15) || ((uintptr_t)workspace & 15))
+        return SASSD_EINVAL;
+    const size_t need = sassd_conv2d_wino4_chain_workspace_bytes(batch, cmax, H, W);
+    if (need == 0 || workspace_bytes < need) return SASSD_ENOSPC;
+    hipStream_t stream = (hipStream_t)stream_;
+    W4Geom G;
+    G.B = batch; G.C = Cin; G.H = H; G.W = W; G.TH = H / 4; G.TW = W / 4; G.T = batch * G.TH * G.TW;
+    G.Tp = w4_tiles_padded(batch, H, W, Cout, geo);
+    float *V = (float *)workspace;
+    float *M = (float *)((char *)workspace + need / 2);
+    if (!(dbg & 16))
+        hipLaunchKernelGGL(wino4_in_sparse_kernel, dim3(cdiv(G.T, 256), D * (C / 4)), dim3(256), 0, stream, feats, C, D, grid, G, V,
+                           tile_map);
+    W4Gemm P;
+    P.U = w_packed; P.V = V; P.M = M; P.scale = nullptr; P.shift = nullptr; P.relu = 0; P.ncols_dev = tile_map;
+    P.np = 36; P.Cin = Cin; P.Cout = Cout; P.ldv = G.Tp; P.ldm = G.Tp; P.ncols = G.Tp;
+    P.su = (size_t)Cin * Cout; P.sv = (size_t)Cin * G.Tp; P.sm = (size_t)Cout * G.Tp;
+    int rc = SASSD_OK;
+    if (!(dbg & 32)) rc = w4_launch(w4_tile(G.T, Cout, geo), P, dbg, stream);
+    if (rc) return rc;
+    if (y && !(dbg & 64)) {
+        W4Geom Go = G;
+        Go.C = Cout;
+        hipLaunchKernelGGL(wino4_out_kernel, dim3(cdiv(G.T, 256), Cout), dim3(256), 0, stream, (const float *)M, Go, Cout, Cout,
+                           scale, shift, relu, y, tile_map);
+    }
     return sassd_launch_status();
 }
 

@@ -586,6 +586,35 @@ def conv2d_wino4_chain(x, prev, w_packed, cin, cout, cmax, batch, h, w, scale, s
     return y
 
 
+def wino4_sparse_grid(batch, d, h, w, device):
+    """Buffer of the pixel -> row index grid of conv2d_wino4_chain_sparse (int32 [B][D][H][W]); None when D > 8."""
+    n = _C.lib().sassd_wino4_sparse_grid_ints(int(batch), int(d), int(h), int(w))
+    return torch.full((n,), -1, dtype=torch.int32, device=device) if n else None
+
+
+def wino4_sparse_prepare(indices, n_ptr, cap, batch, d, h, w, grid, tile_map):
+    """Per frame, from the sparse rows' coordinates: the active-tile map (as wino4_tile_map) and the index grid of
+    conv2d_wino4_chain_sparse (sassd_wino4_sparse_prepare: one fill + two launches)."""
+    _chk_cuda(indices, n_ptr, grid, tile_map)
+    _C.check(_C.lib().sassd_wino4_sparse_prepare(_C.ptr(indices), _C.ptr(n_ptr), int(cap), int(batch), int(d), int(h), int(w),
+                                                 _C.ptr(grid), _C.ptr(tile_map), _C.stream()), "sassd_wino4_sparse_prepare")
+    return grid, tile_map
+
+
+def conv2d_wino4_chain_sparse(feats, d, grid, w_packed, cin, cout, cmax, batch, h, w, scale, shift, relu, y, ws, tile_map,
+                              cfg=None):
+    """The first layer of a Winograd chain straight from sparse rows `feats` [rows, C] (sassd_conv2d_wino4_chain_sparse): what
+    densify(channel_order=1) + conv2d_wino4_chain(x, tile_map=...) compute, bit for bit, without the dense map.  `grid`,
+    `tile_map`: wino4_sparse_prepare of the same rows' coordinates."""
+    _chk_cuda(feats, grid, w_packed, scale, shift, y, ws, tile_map)
+    _C.check(_C.lib().sassd_conv2d_wino4_chain_sparse(_C.ptr(feats), int(feats.shape[1]), int(d), _C.ptr(grid), _C.ptr(w_packed),
+                                                      _C.ptr(scale), _C.ptr(shift), 1 if relu else 0, _C.ptr(y), batch, cin,
+                                                      cout, cmax, h, w, _C.ptr(tile_map),
+                                                      DEFAULT_CFG["wino4"] if cfg is None else int(cfg), _C.ptr(ws), ws.numel(),
+                                                      _C.stream()), "sassd_conv2d_wino4_chain_sparse")
+    return y
+
+
 def conv2d_wino4_pack_weight_narrow(w):
     """w [Cout <= 64, Cin, 3, 3] -> [36][Cin][64] (zero padded) for conv2d_wino4_chain_tail."""
     _chk_cuda(w)

@@ -9,7 +9,9 @@ Stages / reference lines:
   voxelize + mean      points_ops.py:104-164, vxnet.py:110-116          sassd_voxelize
   rulebooks x7         cmn.py:147-173 (spconv get_indice_pairs)         sassd_hash_build / rulebook_subm / rulebook_conv
   sparse convs x14     cmn.py:192-231 (+BN1d+ReLU)                      sassd_spconv_fwd
-  dense()              cmn.py:112-114                                   sassd_densify (d-major channels, conv0 permuted)
+  dense()              cmn.py:112-114                                   sassd_densify (d-major channels, conv0 permuted); the
+                                                                        default fp32 plan builds no dense map: BEV conv0 gathers
+                                                                        the sparse rows (sassd_conv2d_wino4_chain_sparse)
   BEVNet x8            cmn.py:233-282                                   sassd_conv2d_fwd (fp32 MFMA)
   SSD head (fused 1x1) ssd_rotate_head.py:218-235                       sassd_conv2d_fwd
   anchors_mask         kitti.py:333-343                                 sassd_anchor_mask
@@ -81,12 +83,15 @@ class InferencePlan:
                  iou_thr=0.1, cap_k=4096, cap_d=512, device=None, level_cap_factor=2, overlap=True, winograd=True,
                  fused_rulebooks=True, chain_bev=True, pyramid_persistent=False, spconv_cfg=None, wino4_cfg=None,
                  skip_inactive_tiles=True, rb_sync_levels=(0, 1, 2, 3), ps_tail=False, precision="fp32",
-                 sparse_precision="fp32"):
+                 sparse_precision="fp32", dense_entry=False):
         """precision: "fp32" (default) or "bf16" (module docstring).  In bf16 mode the fp32 kernel-selection knobs
         (winograd, chain_bev, wino4_cfg, ps_tail, skip_inactive_tiles) are ignored, and a shape the bf16 kernels do not
         support raises ValueError here (there is no fp32 fall-back).
         sparse_precision: "fp32" (default) or "bf16" -- the 14 sparse convs on bf16 features (module docstring), independent
-        of `precision`; spconv_cfg selects among the fp32 sparse kernels only."""
+        of `precision`; spconv_cfg selects among the fp32 sparse kernels only.
+        dense_entry: False (default) -- in the fp32 / fp32-sparse plan whose conv0 runs on a tile map, conv0's Winograd input
+        transform gathers the level-3 rows through a pixel -> row index grid (sassd_conv2d_wino4_chain_sparse): no dense map is
+        cleared, scattered into and read back, bit-identical.  True: the dense map of every other mode (A/B, tests)."""
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32' or 'bf16', got %r" % (precision,))
         if sparse_precision not in ("fp32", "bf16"):
@@ -182,7 +187,8 @@ class InferencePlan:
         self.feat = [z(max(self.caps), 64, dt=fdt), z(max(self.caps), 64, dt=fdt)]
         self.mean = z(self.caps[0], 4)
         mdt = torch.bfloat16 if self.bf16 else f32          # maps read by a dense conv (bf16 mode: rounded at the store)
-        self.dense = z(B, 64 * D3, H, W, dt=mdt)
+        self._dense_shape, self._dense_dt = (B, 64 * D3, H, W), mdt
+        self._dense = None                                  # the [B, 64 D, H, W] map: allocated by the plans that densify
         self.act = [z(B, 256, H, W, dt=mdt) for _ in range(3)]
         self.head_out = z(B, self.head_c, H, W)
         self.ps_t = [z(B, self.ps_parts, H, W, dt=mdt), z(B, self.ps_parts, H, W)]
@@ -220,6 +226,16 @@ class InferencePlan:
             if n_ints:
                 self.tile_map = z(n_ints, dt=i32)
         self.tmap_ev = torch.cuda.Event()
+        # conv0 straight from the sparse rows (class docstring: dense_entry): needs the tile map; the bf16 modes, keep_middle and
+        # anything that reads `self.dense` stay on (or materialise) the dense map
+        self.sparse_grid = None
+        if not dense_entry and self.tile_map is not None and not self.sparse_bf16 and not self.chain[0]:
+            self.sparse_grid = K.wino4_sparse_grid(B, D3, H, W, dev)
+        self.sparse_entry = self.sparse_grid is not None
+        self._sparse_frame = False                          # the current frame took the sparse entry
+        self._tmap_joined = False
+        if not self.sparse_entry:
+            self._dense_map()
         self.rb_sync_levels = tuple(sorted(int(l) for l in rb_sync_levels))   # levels whose completion the main stream waits
         assert self.rb_sync_levels and self.rb_sync_levels[-1] == 3           # for ((0, 1, 2, 3): one wait per level)
         self.prof = None           # set to {} to collect (name, start_event, end_event) tuples per frame
@@ -311,6 +327,19 @@ class InferencePlan:
         need(K.conv1x1_bf16_infer_supported(w1.shape[1], w1.shape[0], H * W), "the part-sensitive 1x1 (%d -> %d)" % (w1.shape[1], w1.shape[0]))
         self.ps_w1 = K.conv1x1_bf16_pack_weight(w1)
 
+    def _dense_map(self):
+        if self._dense is None:
+            self._dense = torch.zeros(*self._dense_shape, dtype=self._dense_dt, device=self.dev)
+        return self._dense
+
+    @property
+    def dense(self):
+        """The densified level-3 map [B, 64 D, H, W] of the current frame.  A plan on the sparse entry does not build it on the
+        frame path: a read materialises it from the frame's level-3 rows (inspection, tests, per-kernel timing)."""
+        if self._sparse_frame:
+            K.densify(self.sp_out, self.idx[3], self.n[3], self.caps[3], self.shapes[3], self.B, 1, self._dense_map())
+        return self._dense_map()
+
     def _ev(self):
         e = torch.cuda.Event(enable_timing=True)
         e.record()                 # current stream == the stream every sassd kernel is launched on
@@ -392,13 +421,15 @@ class InferencePlan:
         profiles/r05_pyramid_issue_order.txt.  The pyramid in front it is.)"""
         main = torch.cuda.current_stream(self.dev)
         e0 = self._ev() if self.prof is not None else None
+        sparse = self.sparse_entry and densify and not keep_middle
+        self._sparse_frame, self._tmap_joined = sparse, False
         if self.overlap:
             self.side.wait_stream(main)                 # voxel coordinates are ready
             with torch.cuda.stream(self.side):
                 if rulebooks:
                     self.rulebooks()
                 if self.tile_map is not None and densify:
-                    K.wino4_tile_map(self.idx[3], self.n[3], self.caps[3], self.B, self.H, self.W, out=self.tile_map)
+                    self._tile_map(sparse)
                     self.tmap_ev.record()
                 if masks:
                     self.anchor_masks(anchors_mask)     # also coordinate-only work
@@ -406,8 +437,8 @@ class InferencePlan:
         else:
             if rulebooks:
                 self.rulebooks()
-            if self.tile_map is not None and densify:
-                K.wino4_tile_map(self.idx[3], self.n[3], self.caps[3], self.B, self.H, self.W, out=self.tile_map)
+            if self.tile_map is not None and densify and not sparse:
+                self._tile_map(False)
         if not convs:                                   # (measurement: the rulebook pyramid alone)
             return
         x = self.mean
@@ -446,18 +477,35 @@ class InferencePlan:
         if not densify:
             return
         e1 = self._ev() if self.prof is not None else None
-        if self.sparse_bf16:            # the bf16 features unchanged: copied into a bf16 map, widened exactly into an fp32 one
-            K.densify_from_bf16(x, self.idx[3], self.n[3], self.caps[3], self.shapes[3], self.B, 1, self.dense, out_bf16=self.bf16)
+        if sparse:
+            # no dense map: conv0 gathers the rows itself.  What is left of this stage is the index grid (+ tile map): built
+            # from the coordinates on the side stream, joined here -- or built here, on a plan without a side stream
+            if self.overlap:
+                main.wait_event(self.tmap_ev)
+                self._tmap_joined = True
+            else:
+                self._tile_map(True)
+        elif self.sparse_bf16:          # the bf16 features unchanged: copied into a bf16 map, widened exactly into an fp32 one
+            K.densify_from_bf16(x, self.idx[3], self.n[3], self.caps[3], self.shapes[3], self.B, 1, self._dense_map(),
+                                  out_bf16=self.bf16)
         elif self.bf16:
-            K.densify_bf16(x, self.idx[3], self.n[3], self.caps[3], self.shapes[3], self.B, 1, self.dense)
+            K.densify_bf16(x, self.idx[3], self.n[3], self.caps[3], self.shapes[3], self.B, 1, self._dense_map())
         else:
-            K.densify(x, self.idx[3], self.n[3], self.caps[3], self.shapes[3], self.B, 1, self.dense)
+            K.densify(x, self.idx[3], self.n[3], self.caps[3], self.shapes[3], self.B, 1, self._dense_map())
         self._seg("densify", e1)
+
+    def _tile_map(self, sparse):
+        """conv0's active-tile map from the level-3 coordinates; `sparse`: with the index grid of the sparse entry."""
+        if sparse:
+            K.wino4_sparse_prepare(self.idx[3], self.n[3], self.caps[3], self.B, self.D3, self.H, self.W, self.sparse_grid,
+                                   self.tile_map)
+        else:
+            K.wino4_tile_map(self.idx[3], self.n[3], self.caps[3], self.B, self.H, self.W, out=self.tile_map)
 
     def bev_and_heads(self):
         if self.bf16:
             return self._bev_and_heads_bf16()
-        x = self.dense
+        x = None if self._sparse_frame else self._dense_map()
         for i, (wp, cout, ks, scale, shift, wino) in enumerate(self.bev):
             y = self.act[i % 2] if i < 7 else self.act[2]
             e0 = self._ev() if self.prof is not None else None
@@ -468,11 +516,16 @@ class InferencePlan:
                 prev = self.bev[i - 1][3:5] + (True,) if self.chain[i] else None
                 tmap = self.tile_map if i == 0 else None                     # conv0: the active tiles of the sparse map only
                 ptmap = self.tile_map if (i == 1 and self.chain[1]) else None   # conv1 reads conv0's compacted products
-                if tmap is not None and self.overlap:
+                if tmap is not None and self.overlap and not self._tmap_joined:
                     torch.cuda.current_stream(self.dev).wait_event(self.tmap_ev)
-                K.conv2d_wino4_chain(None if self.chain[i] else x, prev, wp, self.bev_cin[i], cout, self.cmax, self.B,
-                                     self.H, self.W, scale, shift, True, None if keep else y, self.wino4_ws, cfg=self.wino4_cfg,
-                                     tile_map=tmap, prev_tile_map=ptmap)
+                if i == 0 and self._sparse_frame:
+                    K.conv2d_wino4_chain_sparse(self.sp_out, self.D3, self.sparse_grid, wp, self.bev_cin[0], cout, self.cmax,
+                                                self.B, self.H, self.W, scale, shift, True, None if keep else y, self.wino4_ws,
+                                                tmap, cfg=self.wino4_cfg)
+                else:
+                    K.conv2d_wino4_chain(None if self.chain[i] else x, prev, wp, self.bev_cin[i], cout, self.cmax, self.B,
+                                         self.H, self.W, scale, shift, True, None if keep else y, self.wino4_ws,
+                                         cfg=self.wino4_cfg, tile_map=tmap, prev_tile_map=ptmap)
             elif wino == 2:
                 K.conv2d_wino_fwd(x, wp, cout, scale, shift, True, y)
             elif wino == 1:
@@ -504,7 +557,7 @@ class InferencePlan:
         self._seg("heads", e0)
 
     def _bev_and_heads_bf16(self):
-        x = self.dense
+        x = self._dense_map()
         for i, (wp, cout, ks, scale, shift) in enumerate(self.bev16):
             y = self.act[i % 2] if i < 7 else self.act[2]
             e0 = self._ev() if self.prof is not None else None
