@@ -194,8 +194,9 @@ int sassd_densify_bf16(const float *feats, const int32_t *indices, const int32_t
                        int batch_size, int channel_order, void *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
- * bf16 sparse backbone (inference only: InferencePlan(sparse_precision="bf16"), test_cfg['sparse_precision']).  Chosen per plan
- * and per call -- no process-wide switch; training stays fp32.  Arithmetic contract:
+ * bf16 sparse backbone, inference (InferencePlan(sparse_precision="bf16"), test_cfg['sparse_precision']).  Chosen per plan
+ * and per call -- no process-wide switch.  (Training has its own opt-in mode and contract: "bf16 sparse backbone, training"
+ * below.)  Arithmetic contract:
  *   first layer (Cin = 4, the voxel means in metres: a bf16 ulp at 70 m is 0.5 m against a 0.05 m voxel)  x fp32 and the fp32
  *            weights, fp32 accumulation, relu(acc * scale + shift) in fp32, the result stored rounded to bf16 (nearest even);
  *   every other layer (submanifold, strided, the 1x1x1 `extra_conv`)  x bf16 as stored; the raw weights rounded once to bf16
@@ -226,6 +227,62 @@ int sassd_spconv_fwd_bf16(const void *x, int x_is_f32, const int32_t *nbr, const
                           void *y_bf16, int cfg, void *stream);
 int sassd_densify_from_bf16(const void *feats, const int32_t *indices, const int32_t *n_ptr, int cap, int C, int D, int H, int W,
                             int batch_size, int channel_order, void *out, int out_is_bf16, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * bf16 sparse backbone, training (opt-in: sassd.autograd.set_sparse_precision("bf16") or train_cfg['sparse_precision'] = 'bf16';
+ * off by default, and with the mode off every launch of a training step is what it was).  Every tensor a sparse kernel GATHERS is
+ * stored bf16; what is read contiguously or feeds statistics stays fp32.  Arithmetic contract:
+ *   first layer (Cin = 4, voxel means in metres)  forward and weight gradient on the fp32 kernels with fp32 operands
+ *            (sassd_spconv_fwd / sassd_spconv_bwd_weight); it has no data gradient.
+ *   every other sparse conv (submanifold, strided, the 1x1x1 `extra_conv`)
+ *     forward          x bf16 as stored; the fp32 master weight rounded once to bf16 by the pack; products exact in fp32, fp32
+ *                      accumulation; the RAW result stored fp32 -- no epilogue; BatchNorm statistics are taken on fp32.
+ *     data gradient    the same kernel on dy (bf16 as stored) with the bf16 image of W[k]^T: on the transposed table, or, for a
+ *                      submanifold layer, on the forward table with the offset-reversed image (the rule of the fp32 path);
+ *                      dx fp32.
+ *     weight gradient  x bf16 (the saved forward operand) and dy bf16, fp32 accumulation, the deterministic two-stage reduction
+ *                      through the caller's workspace (the partial-sum layout and reduce kernel of sassd_spconv_bwd_weight);
+ *                      dw fp32.  An offset without a pair gives exactly 0.
+ *   training BatchNorm1d + ReLU between the layers  arithmetic and running statistics bit-identical to sassd_bn_relu_fwd /
+ *            _bwd; only the store changes: the forward writes its output rounded to bf16 (nearest even) -- the next conv's
+ *            operand, saved for the backward at half the bytes -- and the backward writes the gradient of the raw conv output
+ *            rounded to bf16 -- what the data gradient gathers and the weight gradient reads.  Behind the fp32 first layer the
+ *            backward writes fp32 (sassd_bn_relu_bwd).
+ *   downstream  the auxiliary head's three feature scales and the dense map receive the bf16 features widened exactly to fp32;
+ *            master weights, Adam state and gradients stay fp32.  A conv that is not followed by the fused BatchNorm + ReLU
+ *            rounds its fp32 incoming gradient to bf16 once; fp32 features entering the trunk behind the first layer likewise.
+ *   no float atomics and no hipMemsetAsync in any entry point below; the summation order is a function of the rulebook alone:
+ *            two calls on the same inputs agree bit for bit.
+ * sassd_spconv_train_bf16_supported   (Cin, Cout) in {(16,16), (16,32), (32,32), (32,64), (64,64)} and the transposed pairs of
+ *                                     the data gradients {(32,16), (64,32)}, K = 27 or 1, 0 < cap < 2^25.
+ * sassd_spconv_train_bf16_pack_weight w [K,Cin,Cout] fp32 -> bf16 [K][Cout][Cin] (sassd_spconv_train_bf16_packed_bytes bytes; 0:
+ *                                     no kernel), the pack kernel of sassd_spconv_bf16_pack_weight over the training shape list.
+ *                                     The image of a data gradient is this pack fed W[k]^T ([K,Cout,Cin]; offsets flipped for
+ *                                     the forward-table form) with (Cout, Cin) as its (Cin, Cout).  packed 16-byte aligned.
+ * sassd_spconv_fwd_bf16_raw           y fp32 [cap_out, Cout] = sum_k x[nbr[:,k]] . W[k]: forward and data gradient.  nbr NULL =
+ *                                     identity rulebook with K = 1.  x, w_packed, y 16-byte aligned; cfg is reserved (0).  Rows
+ *                                     past the count are not written.
+ * sassd_spconv_bwd_weight_bf16        dw [27,Cin,Cout] fp32 (+= with accumulate) for the forward pairs; workspace of
+ *                                     sassd_spconv_bwd_weight_bf16_workspace_bytes bytes (0: no kernel), 16-byte aligned like x
+ *                                     and dy; cfg is reserved (0).  SASSD_ENOSPC for a short workspace.
+ * sassd_bn_relu_fwd_bf16out / _bwd_bf16out   sassd_bn_relu_fwd / _bwd with y / dx bf16 [n, C] (8-byte aligned; x and dy 16-byte).
+ * Every entry point returns SASSD_EINVAL for a NULL / misaligned pointer or an unsupported shape before it touches the device.
+ * ---------------------------------------------------------------------------------------------- */
+int sassd_spconv_train_bf16_supported(int K, int Cin, int Cout, int cap);
+size_t sassd_spconv_train_bf16_packed_bytes(int K, int Cin, int Cout);
+int sassd_spconv_train_bf16_pack_weight(const float *w, int K, int Cin, int Cout, void *packed, void *stream);
+int sassd_spconv_fwd_bf16_raw(const void *x_bf16, const int32_t *nbr, const int32_t *n_out_ptr, int cap_out, const void *w_packed,
+                              int K, int Cin, int Cout, float *y, int cfg, void *stream);
+size_t sassd_spconv_bwd_weight_bf16_workspace_bytes(int cap_out, int K, int Cin, int Cout);
+int sassd_spconv_bwd_weight_bf16(const void *x_bf16, const void *dy_bf16, const int32_t *nbr, const int32_t *n_out_ptr, int cap_out,
+                                 int K, int Cin, int Cout, float *dw, int accumulate, int cfg, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+int sassd_bn_relu_fwd_bf16out(const float *x, int n, int C, const float *gamma, const float *beta, float *running_mean,
+                              float *running_var, float momentum, float eps, void *y_bf16, float *save_mean, float *save_invstd,
+                              void *workspace, size_t workspace_bytes, void *stream);
+int sassd_bn_relu_bwd_bf16out(const float *x, const float *dy, int n, int C, const float *gamma, const float *beta,
+                              const float *save_mean, const float *save_invstd, void *dx_bf16, float *dgamma, float *dbeta,
+                              void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * (a9,a10,a12) Dense 2-D convolution (3x3 pad 1 or 1x1), NCHW fp32, on fp32 MFMA (v_mfma_f32_32x32x2_f32),

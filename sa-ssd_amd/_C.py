@@ -69,6 +69,15 @@ _SIGS = {
     "sassd_spconv_bf16_pack_weight": (_I, [_P, _I, _I, _I, _P, _P]),
     "sassd_spconv_fwd_bf16": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P]),
     "sassd_densify_from_bf16": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    # bf16 sparse backbone, training (include/sassd.h "bf16 sparse backbone, training")
+    "sassd_spconv_train_bf16_supported": (_I, [_I, _I, _I, _I]),
+    "sassd_spconv_train_bf16_packed_bytes": (_SZ, [_I, _I, _I]),
+    "sassd_spconv_train_bf16_pack_weight": (_I, [_P, _I, _I, _I, _P, _P]),
+    "sassd_spconv_fwd_bf16_raw": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _P, _I, _P]),
+    "sassd_spconv_bwd_weight_bf16_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "sassd_spconv_bwd_weight_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _SZ, _P]),
+    "sassd_bn_relu_fwd_bf16out": (_I, [_P, _I, _I, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _SZ, _P]),
+    "sassd_bn_relu_bwd_bf16out": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "sassd_conv2d_packed_floats": (_SZ, [_I, _I, _I]),
     "sassd_conv2d_pack_weight": (_I, [_P, _I, _I, _I, _P, _P]),
     "sassd_conv2d_fwd": (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),

@@ -27,6 +27,43 @@ def bev_precision():
     return _BEV_PRECISION
 
 
+_SPARSE_PRECISION = "fp32"
+
+
+def set_sparse_precision(precision):
+    """Arithmetic of the sparse backbone in TRAINING (include/sassd.h "bf16 sparse backbone, training"): "fp32" keeps today's
+    kernels and tensors, "bf16" stores every tensor a sparse kernel gathers -- the conv operands x and the gradients dy of the
+    raw conv outputs -- as bf16 (fp32 accumulation, fp32 raw conv outputs, dx and dw, fp32 master weights; the 4-channel first
+    layer stays fp32).  Independent of set_bev_precision; train_cfg['sparse_precision'] of a detector wins over this setter."""
+    global _SPARSE_PRECISION
+    if precision not in ("fp32", "bf16"):
+        raise ValueError("sparse precision must be 'fp32' or 'bf16', got %r" % (precision,))
+    _SPARSE_PRECISION = precision
+
+
+def sparse_precision():
+    return _SPARSE_PRECISION
+
+
+class sparse_precision_scope:
+    """`with sparse_precision_scope(p):` -- the setter for one block (forward_train resolves train_cfg['sparse_precision'] with it;
+    the autograd nodes recorded inside keep their precision for the backward pass)."""
+
+    def __init__(self, precision):
+        if precision not in ("fp32", "bf16"):
+            raise ValueError("sparse precision must be 'fp32' or 'bf16', got %r" % (precision,))
+        self.precision = precision
+
+    def __enter__(self):
+        global _SPARSE_PRECISION
+        self.prev, _SPARSE_PRECISION = _SPARSE_PRECISION, self.precision
+
+    def __exit__(self, *exc):
+        global _SPARSE_PRECISION
+        _SPARSE_PRECISION = self.prev
+        return False
+
+
 _n_ptr_cache = {}
 
 
@@ -135,6 +172,168 @@ class SparseConvFn(Function):
                 xc = x if n_in > 0 else torch.zeros(1, cin, device=dev)
                 dw = K.spconv_bwd_weight(xc, dyc, nbr, _n_ptr(n_out, dev), nbr.shape[0], cin, cout)
         return dx, dw, None, None, None, None
+
+
+# ---- bf16 sparse backbone, training ---------------------------------------------------------------------------------------
+# A bf16 feature tensor and its gradient have different element types (features bf16, dx fp32), which one autograd tensor cannot
+# express: the engine casts a gradient to the dtype of the tensor it belongs to.  So the bf16 features travel as a PAIR: the bf16
+# tensor itself (no autograd history: SparseConvTensor.features) and an fp32 "carrier" of the same shape that owns the autograd
+# edge (SparseConvTensor._carrier).  The carrier is a stride-0 view of one zero -- it costs no memory and is never read; consumers
+# take the bf16 tensor as their operand and return their fp32 dx as the carrier's gradient, the engine sums the consumers' dx in
+# fp32.  The gradient of a raw conv output (fp32 tensor, bf16 gradient) never crosses an autograd edge: conv + BatchNorm + ReLU
+# are one node (SparseConvBnReluBf16Fn).
+_zero_cache = {}
+
+
+def _carrier(n, c, dev):
+    z = _zero_cache.get(dev)
+    if z is None:
+        z = _zero_cache[dev] = torch.zeros((), dtype=torch.float32, device=dev)
+    return z.expand(n, c)
+
+
+def sparse_bf16_layer_supported(k, cin, cout, cap):
+    """forward, data gradient (Cout -> Cin) and weight gradient of a Cin -> Cout layer all have a bf16 kernel"""
+    from . import _C
+    return (K.spconv_train_bf16_supported(k, cin, cout, cap) and K.spconv_train_bf16_supported(k, cout, cin, cap)
+            and _C.lib().sassd_spconv_bwd_weight_bf16_workspace_bytes(cap, 27, cin, cout) != 0)
+
+
+def _spconv16_pack(weight, kind):
+    """bf16 images of a sparse-conv weight [K, Cin, Cout]: "spconv16" forward, "spconv16_t" W[k]^T (data gradient on the transposed
+    table), "spconv16_t_rev" W[K-1-k]^T (submanifold data gradient on the forward table).  sassd.train.PackPlan refreshes them."""
+    def build():
+        w = weight.detach()
+        if kind == "spconv16":
+            return K.spconv_train_bf16_pack_weight(w.contiguous())
+        if kind == "spconv16_t_rev":
+            w = w.flip(0)
+        return K.spconv_train_bf16_pack_weight(w.transpose(1, 2).contiguous())
+    return WI.image(weight, kind, build)
+
+
+def _sparse_bf16_grads(ctx, xb, weight, dyb):
+    """(dx fp32 | None, dw fp32 | None) of a bf16 sparse conv from its saved bf16 operand and the bf16 gradient of its raw output:
+    the rule of SparseConvFn.backward on the bf16 kernels."""
+    k, cin, cout = weight.shape
+    nbr, n_out = ctx.nbr, ctx.n_out
+    n_in = xb.shape[0]
+    dev = xb.device
+    if n_out == 0:
+        dyb = torch.zeros(1, cout, dtype=torch.bfloat16, device=dev)
+    dx = dw = None
+    if ctx.needs_input_grad[0]:
+        on_fwd = ctx.subm and SparseConvFn.subm_on_forward_table and n_in > 0
+        if nbr is None:
+            dx = K.spconv_fwd_bf16_raw(dyb, None, _n_ptr(n_in, dev), max(n_in, 1), _spconv16_pack(weight, "spconv16_t"), 1, cout, cin)
+        elif on_fwd:
+            dx = K.spconv_fwd_bf16_raw(dyb, nbr, _n_ptr(n_in, dev), nbr.shape[0], _spconv16_pack(weight, "spconv16_t_rev"), 27, cout,
+                                       cin)
+        else:
+            cached = getattr(nbr, "_sassd_transposed", None)
+            if cached is not None and cached[0] == (n_out, n_in):
+                nbr_t = cached[1]
+            else:
+                nbr_t = K.rulebook_transpose(nbr, _n_ptr(n_out, dev), nbr.shape[0], max(n_in, 1))
+                nbr._sassd_transposed = ((n_out, n_in), nbr_t)
+            dx = K.spconv_fwd_bf16_raw(dyb, nbr_t, _n_ptr(n_in, dev), max(n_in, 1), _spconv16_pack(weight, "spconv16_t"), 27, cout, cin)
+        dx = dx[:n_in]
+    if ctx.needs_input_grad[2]:
+        xc = xb if n_in > 0 else torch.zeros(1, cin, dtype=torch.bfloat16, device=dev)
+        if nbr is None:
+            m = max(n_in, 1)
+            dw = K.spconv_bwd_weight_bf16(xc, dyb, _ident_nbr(m, dev), _n_ptr(n_in, dev), m, cin, cout)[13:14]
+        else:
+            dw = K.spconv_bwd_weight_bf16(xc, dyb, nbr, _n_ptr(n_out, dev), nbr.shape[0], cin, cout)
+    return dx, dw
+
+
+def _sparse_bf16_fwd(ctx, xb, weight, nbr, n_out, subm):
+    k, cin, cout = weight.shape
+    dev = xb.device
+    xb = xb.contiguous() if xb.shape[0] > 0 else torch.zeros(1, cin, dtype=torch.bfloat16, device=dev)
+    y = K.spconv_fwd_bf16_raw(xb, nbr, _n_ptr(n_out, dev), max(n_out, 1), _spconv16_pack(weight, "spconv16"), k, cin, cout)
+    ctx.nbr, ctx.n_out = nbr, n_out
+    return y[:n_out]
+
+
+class SparseConvBf16Fn(Function):
+    """Raw bf16 sparse conv that is NOT followed by the fused BatchNorm + ReLU: operand `xb` bf16, result fp32.  `carrier` is the
+    fp32 tensor that receives dx (the carrier of bf16 features, or the fp32 features `xb` was rounded from).  Its fp32 incoming
+    gradient is rounded to bf16 once (nearest even): the kernels gather bf16."""
+
+    @staticmethod
+    def forward(ctx, carrier, xb, weight, nbr, n_out, subm=False):
+        y = _sparse_bf16_fwd(ctx, xb, weight, nbr, n_out, subm)
+        ctx.subm = bool(subm) and nbr is not None and weight.shape[0] == 27 and xb.shape[0] == n_out
+        ctx.save_for_backward(xb, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xb, weight = ctx.saved_tensors
+        dx, dw = _sparse_bf16_grads(ctx, xb, weight, dy.contiguous().to(torch.bfloat16))
+        return dx, None, dw, None, None, None
+
+
+class SparseConvBnReluBf16Fn(Function):
+    """bf16 sparse conv -> training BatchNorm1d -> ReLU as one node: (carrier, xb) -> (carrier of the output, bf16 output).
+    forward   raw = conv(xb) in fp32 (sassd_spconv_fwd_bf16_raw), statistics on fp32, y = bf16(relu(bn(raw)))
+              (sassd_bn_relu_fwd_bf16out); saved: the bf16 operand and the fp32 raw result
+    backward  the summed fp32 gradient of the output -> sassd_bn_relu_bwd_bf16out -> dyb (bf16: what the data gradient gathers and
+              the weight gradient reads) -> dx fp32 (the raw kernel on the data-gradient table / image), dw fp32
+              (sassd_spconv_bwd_weight_bf16)."""
+
+    @staticmethod
+    def forward(ctx, carrier, xb, weight, nbr, n_out, subm, gamma, beta, running_mean, running_var, momentum, eps):
+        raw = _sparse_bf16_fwd(ctx, xb, weight, nbr, n_out, subm)
+        ctx.subm = bool(subm) and nbr is not None and weight.shape[0] == 27 and xb.shape[0] == n_out
+        yb, mean, invstd = K.bn_relu_fwd(raw, gamma.detach().contiguous(), beta.detach().contiguous(), running_mean, running_var,
+                                         momentum, eps, out_bf16=True)
+        ctx.save_for_backward(xb, weight, raw, gamma, beta, mean, invstd)
+        ctx.mark_non_differentiable(yb)
+        return _carrier(n_out, weight.shape[2], raw.device), yb
+
+    @staticmethod
+    def backward(ctx, g, _gyb):
+        xb, weight, raw, gamma, beta, mean, invstd = ctx.saved_tensors
+        dyb, dg, db = K.bn_relu_bwd(raw, g.contiguous(), gamma.detach().contiguous(), beta.detach().contiguous(), mean, invstd,
+                                    out_bf16=True)
+        dx, dw = _sparse_bf16_grads(ctx, xb, weight, dyb)
+        return dx, None, dw, None, None, None, dg, db, None, None, None, None
+
+
+class BnReluBf16OutFn(Function):
+    """BnReluFn behind an fp32 conv (the 4-channel first layer) in bf16 sparse mode: x fp32 -> (carrier, bf16 output).  The backward
+    is BnReluFn's: its dx feeds an fp32 conv and is written fp32."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps):
+        x = x.contiguous()
+        yb, mean, invstd = K.bn_relu_fwd(x, gamma.detach().contiguous(), beta.detach().contiguous(), running_mean, running_var,
+                                         momentum, eps, out_bf16=True)
+        ctx.save_for_backward(x, gamma, beta, mean, invstd)
+        ctx.mark_non_differentiable(yb)
+        return _carrier(x.shape[0], x.shape[1], x.device), yb
+
+    @staticmethod
+    def backward(ctx, g, _gyb):
+        x, gamma, beta, mean, invstd = ctx.saved_tensors
+        dx, dg, db = K.bn_relu_bwd(x, g.contiguous(), gamma.detach().contiguous(), beta.detach().contiguous(), mean, invstd)
+        return dx, dg, db, None, None, None, None
+
+
+class WidenBf16Fn(Function):
+    """bf16 features widened exactly to fp32 for a consumer outside the sparse convs (auxiliary head, densify); the consumer's
+    fp32 gradient goes to the carrier unchanged."""
+
+    @staticmethod
+    def forward(ctx, carrier, xb):
+        return xb.float()
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None
 
 
 def _conv_any(x, weight, ks, packed=None, wino=None, shift=None, wino4=None):

@@ -130,9 +130,22 @@ struct BnApplyArgs {
     int n, C, nb;
     const double *part;
     const float *gamma, *beta;
-    float *y, *mean, *invstd, *rmean, *rvar;
+    void *y;                 // fp32, or bf16 (nearest even) for the _bf16out entry points
+    float *mean, *invstd, *rmean, *rvar;
     float momentum, eps;
 };
+
+// the one store of the two apply kernels: four channels of a row as fp32, or rounded to bf16 (nearest even) by a plain cast
+template <typename TO>
+__device__ __forceinline__ void bn_store4(void *dst, size_t i, const f32x4 &o)
+{
+    if constexpr (sizeof(TO) == 4) {
+        ((f32x4 *)dst)[i] = o;
+    } else {
+        ((ushort4 *)dst)[i] = make_ushort4(__builtin_bit_cast(unsigned short, (__bf16)o[0]), __builtin_bit_cast(unsigned short, (__bf16)o[1]),
+                                           __builtin_bit_cast(unsigned short, (__bf16)o[2]), __builtin_bit_cast(unsigned short, (__bf16)o[3]));
+    }
+}
 
 __global__ void __launch_bounds__(256) bn_finalize_kernel(BnApplyArgs P)
 {
@@ -161,6 +174,7 @@ __global__ void __launch_bounds__(256) bn_finalize_kernel(BnApplyArgs P)
     }
 }
 
+template <typename TO>
 __global__ void __launch_bounds__(256) bn_apply_relu_kernel(BnApplyArgs P)
 {
     __shared__ float s_mean[256], s_scale[256], s_shift[256];
@@ -181,7 +195,7 @@ __global__ void __launch_bounds__(256) bn_apply_relu_kernel(BnApplyArgs P)
             const float z = fmaf(v[j] - s_mean[c + j], s_scale[c + j], s_shift[c + j]);   // (= the backward's expression)
             o[j] = z > 0.f ? z : 0.f;
         }
-        ((f32x4 *)P.y)[i] = o;
+        bn_store4<TO>(P.y, i, o);
     }
 }
 
@@ -190,7 +204,8 @@ struct BnBwdArgs {
     int n, C, nb, rows_per_block;
     const float *mean, *invstd, *gamma, *beta;
     double *part;            // [nb][2][C]
-    float *dx, *dgamma, *dbeta;
+    void *dx;                // fp32, or bf16 (nearest even) for the _bf16out entry points
+    float *dgamma, *dbeta;
 };
 
 __global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(BnBwdArgs P)
@@ -250,6 +265,7 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_kernel(BnBwdArgs P)
     }
 }
 
+template <typename TO>
 __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(BnBwdArgs P)
 {
     __shared__ float s_mean[256], s_is[256], s_g[256], s_b[256], s_db[256], s_dg[256];
@@ -276,7 +292,7 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(BnBwdArgs P)
             const float dz = z > 0.f ? g[j] : 0.f;
             o[j] = s_g[c + j] * s_is[c + j] * (dz - s_db[c + j] * inv_n - xh * s_dg[c + j] * inv_n);
         }
-        ((f32x4 *)P.dx)[i] = o;
+        bn_store4<TO>(P.dx, i, o);
     }
 }
 
@@ -304,11 +320,12 @@ extern "C" size_t sassd_bn_relu_workspace_bytes(int C)
     return C < 1 ? 0 : align_up((size_t)kBnMaxBlocks * 4 * C * sizeof(double), 256);
 }
 
-extern "C" int sassd_bn_relu_fwd(const float *x, int n, int C, const float *gamma, const float *beta,
-                                 float *running_mean, float *running_var, float momentum, float eps, float *y,
+static int bn_relu_fwd_any(const float *x, int n, int C, const float *gamma, const float *beta,
+                                 float *running_mean, float *running_var, float momentum, float eps, void *y, int y_bf16,
                                  float *save_mean, float *save_invstd, void *workspace, size_t workspace_bytes,
                                  void *stream_)
 {
+    if (y_bf16 && ((uintptr_t)y & 7)) return SASSD_EINVAL;
     if (!x || !gamma || !beta || !y || !save_mean || !save_invstd || !workspace || !bn_shape_ok(n, C) ||
         (!running_mean) != (!running_var))
         return SASSD_EINVAL;
@@ -326,14 +343,36 @@ extern "C" int sassd_bn_relu_fwd(const float *x, int n, int C, const float *gamm
     Q.mean = save_mean; Q.invstd = save_invstd; Q.rmean = running_mean; Q.rvar = running_var;
     Q.momentum = momentum; Q.eps = eps;
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, s, Q);
-    hipLaunchKernelGGL(bn_apply_relu_kernel, dim3(bn_apply_blocks(n, C)), dim3(256), 0, s, Q);
+    if (y_bf16) hipLaunchKernelGGL(bn_apply_relu_kernel<unsigned short>, dim3(bn_apply_blocks(n, C)), dim3(256), 0, s, Q);
+    else hipLaunchKernelGGL(bn_apply_relu_kernel<float>, dim3(bn_apply_blocks(n, C)), dim3(256), 0, s, Q);
     return sassd_launch_status();
 }
 
-extern "C" int sassd_bn_relu_bwd(const float *x, const float *dy, int n, int C, const float *gamma, const float *beta,
-                                 const float *save_mean, const float *save_invstd, float *dx, float *dgamma,
+extern "C" int sassd_bn_relu_fwd(const float *x, int n, int C, const float *gamma, const float *beta,
+                                 float *running_mean, float *running_var, float momentum, float eps, float *y,
+                                 float *save_mean, float *save_invstd, void *workspace, size_t workspace_bytes,
+                                 void *stream_)
+{
+    return bn_relu_fwd_any(x, n, C, gamma, beta, running_mean, running_var, momentum, eps, y, 0, save_mean, save_invstd, workspace,
+                           workspace_bytes, stream_);
+}
+
+// sassd_bn_relu_fwd with the output rounded to bf16 (nearest even) at the store: the same statistics, the same arithmetic
+extern "C" int sassd_bn_relu_fwd_bf16out(const float *x, int n, int C, const float *gamma, const float *beta,
+                                         float *running_mean, float *running_var, float momentum, float eps, void *y_bf16,
+                                         float *save_mean, float *save_invstd, void *workspace, size_t workspace_bytes,
+                                         void *stream_)
+{
+    if ((uintptr_t)x & 15) return SASSD_EINVAL;
+    return bn_relu_fwd_any(x, n, C, gamma, beta, running_mean, running_var, momentum, eps, y_bf16, 1, save_mean, save_invstd,
+                           workspace, workspace_bytes, stream_);
+}
+
+static int bn_relu_bwd_any(const float *x, const float *dy, int n, int C, const float *gamma, const float *beta,
+                                 const float *save_mean, const float *save_invstd, void *dx, int dx_bf16, float *dgamma,
                                  float *dbeta, void *workspace, size_t workspace_bytes, void *stream_)
 {
+    if (dx_bf16 && ((uintptr_t)dx & 7)) return SASSD_EINVAL;
     if (!x || !dy || !gamma || !beta || !save_mean || !save_invstd || !dx || !dgamma || !dbeta || !workspace ||
         !bn_shape_ok(n, C))
         return SASSD_EINVAL;
@@ -347,6 +386,25 @@ extern "C" int sassd_bn_relu_bwd(const float *x, const float *dy, int n, int C, 
     P.dx = dx; P.dgamma = dgamma; P.dbeta = dbeta;
     hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(P.nb), dim3(256), 0, s, P);
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, s, P);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(bn_apply_blocks(n, C)), dim3(256), 0, s, P);
+    if (dx_bf16) hipLaunchKernelGGL(bn_bwd_apply_kernel<unsigned short>, dim3(bn_apply_blocks(n, C)), dim3(256), 0, s, P);
+    else hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(bn_apply_blocks(n, C)), dim3(256), 0, s, P);
     return sassd_launch_status();
+}
+
+extern "C" int sassd_bn_relu_bwd(const float *x, const float *dy, int n, int C, const float *gamma, const float *beta,
+                                 const float *save_mean, const float *save_invstd, float *dx, float *dgamma,
+                                 float *dbeta, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    return bn_relu_bwd_any(x, dy, n, C, gamma, beta, save_mean, save_invstd, dx, 0, dgamma, dbeta, workspace, workspace_bytes,
+                           stream_);
+}
+
+// sassd_bn_relu_bwd with dx rounded to bf16 (nearest even) at the store; dgamma / dbeta are its fp32 values bit for bit
+extern "C" int sassd_bn_relu_bwd_bf16out(const float *x, const float *dy, int n, int C, const float *gamma, const float *beta,
+                                         const float *save_mean, const float *save_invstd, void *dx_bf16, float *dgamma,
+                                         float *dbeta, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (((uintptr_t)x | (uintptr_t)dy) & 15) return SASSD_EINVAL;
+    return bn_relu_bwd_any(x, dy, n, C, gamma, beta, save_mean, save_invstd, dx_bf16, 1, dgamma, dbeta, workspace, workspace_bytes,
+                           stream_);
 }

@@ -884,6 +884,8 @@ int launch_wgrad(const float *x, const float *dy, const int32_t *nbr, const int3
     return sassd_launch_status();
 }
 
+#include "spconv_bf16_train.h"
+
 }  // namespace
 
 extern "C" int sassd_rulebook_transpose(const int32_t *nbr, const int32_t *n_out_ptr, int cap_out, int32_t *nbrT,
@@ -1074,4 +1076,79 @@ extern "C" int sassd_densify_from_bf16(const void *feats, const int32_t *indices
         hipLaunchKernelGGL(densify_from_bf16_kernel<float>, dim3(cdiv(cap * C, 256)), dim3(256), 0, stream, f, indices, n_ptr,
                            cap, C, D, H, W, channel_order, (float *)out);
     return sassd_launch_status();
+}
+
+// ---- bf16 sparse backbone, training (set_sparse_precision("bf16") / train_cfg['sparse_precision']; contract in include/sassd.h) ----
+extern "C" int sassd_spconv_train_bf16_supported(int K, int Cin, int Cout, int cap)
+{
+    // forward pairs and the transposed pairs of the data gradients; the 4-channel first layer stays on the fp32 kernels
+    if (cap <= 0 || cap >= (1 << 25)) return 0;              // packed pair-list entries: input row << 6 | local row
+    const bool shape = (Cin == 16 && (Cout == 16 || Cout == 32)) || (Cin == 32 && (Cout == 16 || Cout == 32 || Cout == 64)) ||
+                       (Cin == 64 && (Cout == 32 || Cout == 64));
+    return shape && (K == kK || K == 1);
+}
+
+extern "C" size_t sassd_spconv_train_bf16_packed_bytes(int K, int Cin, int Cout)
+{
+    return sassd_spconv_train_bf16_supported(K, Cin, Cout, 1) ? (size_t)K * Cin * Cout * sizeof(unsigned short) : 0;
+}
+
+// w [K][Cin][Cout] fp32 -> [K][Cout][Cin] bf16 (nearest even): the pack kernel of sassd_spconv_bf16_pack_weight over the training
+// shape list.  A data-gradient image is this pack fed W[k]^T (offset-flipped for the forward-table form) with (Cout, Cin) swapped.
+extern "C" int sassd_spconv_train_bf16_pack_weight(const float *w, int K, int Cin, int Cout, void *packed, void *stream_)
+{
+    if (!w || !packed || !sassd_spconv_train_bf16_supported(K, Cin, Cout, 1)) return SASSD_EINVAL;
+    if (((uintptr_t)w & 3) || ((uintptr_t)packed & 15)) return SASSD_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int total = K * Cin * Cout;
+    hipLaunchKernelGGL(pack_weight_bf16_kernel, dim3(cdiv(total, 256)), dim3(256), 0, stream, w, K, Cin, Cout,
+                       (unsigned short *)packed);
+    return sassd_launch_status();
+}
+
+extern "C" int sassd_spconv_fwd_bf16_raw(const void *x_bf16, const int32_t *nbr, const int32_t *n_out_ptr, int cap_out,
+                                         const void *w_packed, int K, int Cin, int Cout, float *y, int cfg, void *stream_)
+{
+    if (!x_bf16 || !n_out_ptr || !w_packed || !y || cfg != 0) return SASSD_EINVAL;
+    if (!sassd_spconv_train_bf16_supported(K, Cin, Cout, cap_out)) return SASSD_EINVAL;
+    if (nbr ? (K != kK) : (K != 1)) return SASSD_EINVAL;
+    if ((((uintptr_t)x_bf16 | (uintptr_t)w_packed | (uintptr_t)y) & 15) || ((uintptr_t)nbr & 3) || ((uintptr_t)n_out_ptr & 3))
+        return SASSD_EINVAL;
+    hipStream_t stream = (hipStream_t)stream_;
+    const unsigned short *xb = (const unsigned short *)x_bf16, *wb = (const unsigned short *)w_packed;
+#define SP_RAW16(CI, CO) if (Cin == CI && Cout == CO) return launch_raw16<CI, CO>(xb, nbr, n_out_ptr, cap_out, wb, y, stream);
+    SP_RAW16(16, 16) SP_RAW16(16, 32) SP_RAW16(32, 32) SP_RAW16(32, 64) SP_RAW16(64, 64) SP_RAW16(32, 16) SP_RAW16(64, 32)
+#undef SP_RAW16
+    return SASSD_EINVAL;
+}
+
+static bool wgrad16_shape(int Cin, int Cout)
+{
+    return (Cin == 16 && (Cout == 16 || Cout == 32)) || (Cin == 32 && (Cout == 32 || Cout == 64)) || (Cin == 64 && Cout == 64);
+}
+
+extern "C" size_t sassd_spconv_bwd_weight_bf16_workspace_bytes(int cap_out, int K, int Cin, int Cout)
+{
+    if (K != kK || !wgrad16_shape(Cin, Cout)) return 0;
+    return sassd_spconv_bwd_weight_workspace_bytes(cap_out, K, Cin, Cout);       // the same [chunk][offset][Cin][Cout] partials
+}
+
+extern "C" int sassd_spconv_bwd_weight_bf16(const void *x_bf16, const void *dy_bf16, const int32_t *nbr, const int32_t *n_out_ptr,
+                                            int cap_out, int K, int Cin, int Cout, float *dw, int accumulate, int cfg,
+                                            void *workspace, size_t workspace_bytes, void *stream_)
+{
+    if (!x_bf16 || !dy_bf16 || !nbr || !n_out_ptr || !dw || !workspace || cap_out <= 0 || K != kK || cfg != 0) return SASSD_EINVAL;
+    if (!wgrad16_shape(Cin, Cout)) return SASSD_EINVAL;
+    if ((((uintptr_t)x_bf16 | (uintptr_t)dy_bf16 | (uintptr_t)workspace) & 15) ||
+        (((uintptr_t)dw | (uintptr_t)nbr | (uintptr_t)n_out_ptr) & 3))
+        return SASSD_EINVAL;
+    if (workspace_bytes < sassd_spconv_bwd_weight_bf16_workspace_bytes(cap_out, K, Cin, Cout)) return SASSD_ENOSPC;
+    hipStream_t stream = (hipStream_t)stream_;
+    const unsigned short *xb = (const unsigned short *)x_bf16, *db = (const unsigned short *)dy_bf16;
+    float *part = (float *)workspace;
+#define SP_WG16(CI, CO) \
+    if (Cin == CI && Cout == CO) return launch_wgrad16<CI, CO>(xb, db, nbr, n_out_ptr, cap_out, part, dw, accumulate ? 1 : 0, stream);
+    SP_WG16(16, 16) SP_WG16(16, 32) SP_WG16(32, 32) SP_WG16(32, 64) SP_WG16(64, 64)
+#undef SP_WG16
+    return SASSD_EINVAL;
 }

@@ -18,11 +18,12 @@
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
-template <int CIN, int COUT, int NW, int WPS>
-__global__ void __launch_bounds__(NW * 64, WPS)
-spconv_bf16_kernel(const unsigned short *__restrict__ x, const int32_t *__restrict__ nbr, const int32_t *__restrict__ n_ptr,
-                   int cap, const unsigned short *__restrict__ wp, const float *__restrict__ scale,
-                   const float *__restrict__ shift, int relu, unsigned short *__restrict__ y)
+// RAW (training, spconv_bf16_train.h): the same rows, the fp32 accumulator stored as it is -- no scale / shift / ReLU, no rounding.
+template <int CIN, int COUT, int NW, bool RAW>
+__device__ __forceinline__ void
+spconv_bf16_rows(const unsigned short *__restrict__ x, const int32_t *__restrict__ nbr, const int32_t *__restrict__ n_ptr,
+                 int cap, const unsigned short *__restrict__ wp, const float *__restrict__ scale,
+                 const float *__restrict__ shift, int relu, void *__restrict__ y_)
 {
     static_assert(COUT == 16 || COUT == 32 || COUT == 64, "4x4x4 broadcast tile: 16 / 32 / 64 output channels");
     static_assert(CIN % 16 == 0, "a lane's channel quarter is a whole number of 4-channel MFMA steps");
@@ -237,6 +238,11 @@ spconv_bf16_kernel(const unsigned short *__restrict__ x, const int32_t *__restri
             const float4 p = *(const float4 *)(src + w * RW * COUT);
             v.x += p.x; v.y += p.y; v.z += p.z; v.w += p.w;
         }
+        if constexpr (RAW) {
+            *(float4 *)((float *)y_ + (size_t)(row0 + RS * r) * COUT + c4 * 4) = v;
+            continue;
+        }
+        unsigned short *y = (unsigned short *)y_;
         const float4 sc = scale ? *(const float4 *)(scale + c4 * 4) : make_float4(1.f, 1.f, 1.f, 1.f);
         const float4 sh = shift ? *(const float4 *)(shift + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
         v.x = v.x * sc.x + sh.x; v.y = v.y * sc.y + sh.y; v.z = v.z * sc.z + sh.z; v.w = v.w * sc.w + sh.w;
@@ -245,6 +251,15 @@ spconv_bf16_kernel(const unsigned short *__restrict__ x, const int32_t *__restri
                                        __builtin_bit_cast(unsigned short, (__bf16)v.z), __builtin_bit_cast(unsigned short, (__bf16)v.w));
         *(ushort4 *)(y + (size_t)(row0 + RS * r) * COUT + c4 * 4) = o;
     }
+}
+
+template <int CIN, int COUT, int NW, int WPS>
+__global__ void __launch_bounds__(NW * 64, WPS)
+spconv_bf16_kernel(const unsigned short *__restrict__ x, const int32_t *__restrict__ nbr, const int32_t *__restrict__ n_ptr,
+                   int cap, const unsigned short *__restrict__ wp, const float *__restrict__ scale,
+                   const float *__restrict__ shift, int relu, unsigned short *__restrict__ y)
+{
+    spconv_bf16_rows<CIN, COUT, NW, false>(x, nbr, n_ptr, cap, wp, scale, shift, relu, y);
 }
 
 template <int COUT, int NW>

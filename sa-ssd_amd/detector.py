@@ -365,7 +365,7 @@ class SpMiddleFHD(nn.Module):
                                         min(self.aux_bin, 4 * self.aux_voxel_size[0] * mult), batch_size)
             nn_idx.append(idx)
             nn_d2.append(d2)
-        sums = AuxHeadFn.apply(middle[0].features, middle[1].features, middle[2].features, self.point_fc.weight,
+        sums = AuxHeadFn.apply(middle[0].features_f32(), middle[1].features_f32(), middle[2].features_f32(), self.point_fc.weight,
                                self.point_cls.weight, self.point_reg.weight, nn_idx, nn_d2, label, target, npos,
                                bool(deterministic))
         n = len(gt_bboxes)
@@ -394,7 +394,7 @@ class SpMiddleFHD(nn.Module):
         off, vs = _const(ind.device, offset), _const(ind.device, voxel_size)
         out = ind.clone()
         out[:, 1:] = ind[:, 1:].flip(1) * vs + off + .5 * vs          # columns (3,2,1) without an index tensor upload
-        return tensor.features, out
+        return tensor.features_f32(), out
 
     def forward(self, voxel_features, coors, batch_size, is_test=False, indice_dict=None):
         x = spconv.SparseConvTensor(voxel_features, coors.int(), self.sparse_shape, batch_size)
@@ -916,8 +916,23 @@ class SingleStageDetector(nn.Module):
         cfg = self.train_cfg or {}
         return bool(cfg.get('deterministic', False)) or torch.are_deterministic_algorithms_enabled()
 
+    def sparse_training_precision(self):
+        """Precision of the sparse backbone in training: the optional top-level train_cfg['sparse_precision'] ("fp32" / "bf16"),
+        else sassd.autograd.sparse_precision() (the module-level setter)."""
+        from . import autograd as AG
+        p = (self.train_cfg or {}).get('sparse_precision')
+        p = AG.sparse_precision() if p is None else p
+        if p not in ("fp32", "bf16"):
+            raise ValueError("train_cfg['sparse_precision'] must be 'fp32' or 'bf16', got %r" % (p,))
+        return p
+
     def forward_train(self, img, img_meta, **kwargs):
         """single_stage.py:75-108 -> dict of loss tensors."""
+        from . import autograd as AG
+        with AG.sparse_precision_scope(self.sparse_training_precision()):
+            return self._forward_train(img, img_meta, **kwargs)
+
+    def _forward_train(self, img, img_meta, **kwargs):
         batch_size = len(img_meta)
         det = self.deterministic_training()
         ret = self.merge_second_batch(kwargs)

@@ -425,6 +425,55 @@ def densify_from_bf16(feats, indices, n_ptr, cap, shape, batch_size, channel_ord
     return out
 
 
+# ---- bf16 sparse backbone, training (set_sparse_precision("bf16")): bf16 gathered operands, fp32 raw results ----------------------
+def spconv_train_bf16_supported(k, cin, cout, cap):
+    return bool(_C.lib().sassd_spconv_train_bf16_supported(k, cin, cout, cap))
+
+
+def spconv_train_bf16_pack_weight(w):
+    """w [K, Cin, Cout] fp32 -> bf16 image [K][Cout][Cin] (nearest even) of a Cin -> Cout conv for spconv_fwd_bf16_raw.  The image
+    of a data gradient is this pack of W[k]^T ([K, Cout, Cin]; offset-flipped for the forward-table form)."""
+    _chk_cuda(w)
+    k, cin, cout = w.shape
+    L = _C.lib()
+    nbytes = L.sassd_spconv_train_bf16_packed_bytes(k, cin, cout)
+    if not nbytes:
+        raise ValueError("no bf16 training sparse-conv kernel for K=%d, %d -> %d" % (k, cin, cout))
+    packed = torch.empty(nbytes // 2, dtype=torch.int16, device=w.device)
+    _C.check(L.sassd_spconv_train_bf16_pack_weight(_C.ptr(w), k, cin, cout, _C.ptr(packed), _C.stream()),
+             "sassd_spconv_train_bf16_pack_weight")
+    return packed
+
+
+def spconv_fwd_bf16_raw(x, nbr, n_out_ptr, cap_out, w_packed, k, cin, cout, y=None):
+    """raw sparse conv (forward, or a data gradient on its table and image): x bf16 [rows, Cin] -> y fp32 [cap_out, Cout]."""
+    _chk_cuda(x, nbr, w_packed)
+    assert x.dtype == torch.bfloat16 and x.shape[1] == cin
+    if y is None:
+        y = torch.empty(cap_out, cout, dtype=torch.float32, device=x.device)
+    assert y.dtype == torch.float32 and y.is_contiguous()
+    _C.check(_C.lib().sassd_spconv_fwd_bf16_raw(_C.ptr(x), _C.ptr(nbr), _C.ptr(n_out_ptr), cap_out, _C.ptr(w_packed), k, cin,
+                                                cout, _C.ptr(y), 0, _C.stream()), "sassd_spconv_fwd_bf16_raw")
+    return y
+
+
+def spconv_bwd_weight_bf16(x, dy, nbr, n_out_ptr, cap_out, cin, cout, dw=None, accumulate=False):
+    """dw [27, Cin, Cout] fp32 from x bf16 [rows, Cin] and dy bf16 [cap_out, Cout]; fixed-order two-stage reduction."""
+    _chk_cuda(x, dy, nbr)
+    assert x.dtype == torch.bfloat16 and dy.dtype == torch.bfloat16
+    L = _C.lib()
+    if dw is None:
+        dw = torch.empty(27, cin, cout, dtype=torch.float32, device=x.device)
+    wsb = L.sassd_spconv_bwd_weight_bf16_workspace_bytes(cap_out, 27, cin, cout)
+    if not wsb:
+        raise ValueError("no bf16 sparse weight-gradient kernel for %d -> %d" % (cin, cout))
+    ws = workspace("spconv_wgrad", wsb, x.device)
+    _C.check(L.sassd_spconv_bwd_weight_bf16(_C.ptr(x), _C.ptr(dy), _C.ptr(nbr), _C.ptr(n_out_ptr), cap_out, 27, cin, cout,
+                                            _C.ptr(dw), 1 if accumulate else 0, 0, _C.ptr(ws), wsb, _C.stream()),
+             "sassd_spconv_bwd_weight_bf16")
+    return dw
+
+
 # --------------------------------------------------------------------------------------------------
 def conv2d_pack_weight(w):
     """w [Cout, Cin, k, k] f32 cuda (torch layout) -> packed [Cin/8][k*k][8][CoutPad]."""
@@ -1205,31 +1254,34 @@ def bn_relu_supported(n, c):
     return n >= 1 and 4 <= c <= 256 and c % 4 == 0 and 256 % c == 0
 
 
-def bn_relu_fwd(x, gamma, beta, running_mean, running_var, momentum, eps):
-    """-> (y, save_mean, save_invstd); running statistics updated in place (pass None for both to skip)."""
+def bn_relu_fwd(x, gamma, beta, running_mean, running_var, momentum, eps, out_bf16=False):
+    """-> (y, save_mean, save_invstd); running statistics updated in place (pass None for both to skip).  out_bf16: y is the
+    same result rounded to bf16 at the store (sassd_bn_relu_fwd_bf16out)."""
     _chk_cuda(x, gamma, beta, running_mean, running_var)
     n, c = x.shape
-    y = torch.empty_like(x)
+    y = torch.empty_like(x, dtype=torch.bfloat16 if out_bf16 else None)
     mean = torch.empty(c, dtype=torch.float32, device=x.device)
     invstd = torch.empty(c, dtype=torch.float32, device=x.device)
     ws = _bn_workspace(x.device)
-    _C.check(_C.lib().sassd_bn_relu_fwd(_C.ptr(x), n, c, _C.ptr(gamma), _C.ptr(beta), _C.ptr(running_mean),
-                                        _C.ptr(running_var), float(momentum), float(eps), _C.ptr(y), _C.ptr(mean),
-                                        _C.ptr(invstd), _C.ptr(ws), ws.numel(), _C.stream()), "sassd_bn_relu_fwd")
+    L = _C.lib()
+    fn = L.sassd_bn_relu_fwd_bf16out if out_bf16 else L.sassd_bn_relu_fwd
+    _C.check(fn(_C.ptr(x), n, c, _C.ptr(gamma), _C.ptr(beta), _C.ptr(running_mean), _C.ptr(running_var), float(momentum),
+                float(eps), _C.ptr(y), _C.ptr(mean), _C.ptr(invstd), _C.ptr(ws), ws.numel(), _C.stream()), "sassd_bn_relu_fwd")
     return y, mean, invstd
 
 
-def bn_relu_bwd(x, dy, gamma, beta, mean, invstd):
-    """-> (dx, dgamma, dbeta)."""
+def bn_relu_bwd(x, dy, gamma, beta, mean, invstd, out_bf16=False):
+    """-> (dx, dgamma, dbeta).  out_bf16: dx rounded to bf16 at the store (sassd_bn_relu_bwd_bf16out)."""
     _chk_cuda(x, dy, gamma, beta, mean, invstd)
     n, c = x.shape
-    dx = torch.empty_like(x)
+    dx = torch.empty_like(x, dtype=torch.bfloat16 if out_bf16 else None)
     dg = torch.empty(c, dtype=torch.float32, device=x.device)
     db = torch.empty(c, dtype=torch.float32, device=x.device)
     ws = _bn_workspace(x.device)
-    _C.check(_C.lib().sassd_bn_relu_bwd(_C.ptr(x), _C.ptr(dy), n, c, _C.ptr(gamma), _C.ptr(beta), _C.ptr(mean),
-                                        _C.ptr(invstd), _C.ptr(dx), _C.ptr(dg), _C.ptr(db), _C.ptr(ws), ws.numel(),
-                                        _C.stream()), "sassd_bn_relu_bwd")
+    L = _C.lib()
+    fn = L.sassd_bn_relu_bwd_bf16out if out_bf16 else L.sassd_bn_relu_bwd
+    _C.check(fn(_C.ptr(x), _C.ptr(dy), n, c, _C.ptr(gamma), _C.ptr(beta), _C.ptr(mean), _C.ptr(invstd), _C.ptr(dx), _C.ptr(dg),
+                _C.ptr(db), _C.ptr(ws), ws.numel(), _C.stream()), "sassd_bn_relu_bwd")
     return dx, dg, db
 
 

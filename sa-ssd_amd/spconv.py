@@ -15,6 +15,7 @@ from torch import nn
 
 from . import kernels as K
 from . import weight_images
+from . import autograd as AG
 from .autograd import BnReluFn, DensifyFn, SparseConvFn, count_bn_batch, _n_ptr as _cached_n_ptr
 
 
@@ -26,6 +27,15 @@ class SparseConvTensor:
         self.batch_size = int(batch_size)
         self.indice_dict = {}          # indice_key -> (out_indices, nbr, out_shape, hash table)
         self._table = None
+        # bf16 sparse training (autograd.set_sparse_precision("bf16")): `features` is then a bf16 tensor without autograd history
+        # and `_carrier` the fp32 stride-0 tensor that owns its autograd edge (see autograd.py); features_f32() for everyone else
+        self._carrier = None
+
+    def features_f32(self):
+        """The features as a differentiable fp32 tensor: `features` itself, or bf16 training features widened exactly."""
+        if self._carrier is not None:
+            return AG.WidenBf16Fn.apply(self._carrier, self.features)
+        return self.features
 
     @property
     def spatial_size(self):
@@ -46,10 +56,11 @@ class SparseConvTensor:
         d, h, w = self.spatial_shape
         c = self.features.shape[1]
         n = self.indices.shape[0]
-        if torch.is_grad_enabled() and self.features.requires_grad:
-            out = DensifyFn.apply(self.features.float(), self.indices.int().contiguous(), (d, h, w), self.batch_size)
+        feats = self.features_f32()
+        if torch.is_grad_enabled() and feats.requires_grad:
+            out = DensifyFn.apply(feats.float(), self.indices.int().contiguous(), (d, h, w), self.batch_size)
             return out if channels_first else out.permute(0, 2, 3, 4, 1).contiguous()
-        out = K.densify(self.features.contiguous(), self.indices.int().contiguous(), self._n_ptr(), max(n, 1),
+        out = K.densify(feats.contiguous(), self.indices.int().contiguous(), self._n_ptr(), max(n, 1),
                         (d, h, w), self.batch_size, 0)
         out = out.view(self.batch_size, c, d, h, w)
         return out if channels_first else out.permute(0, 2, 3, 4, 1).contiguous()
@@ -128,9 +139,55 @@ class SparseConvolution(nn.Module):
             inp.indice_dict[self.indice_key] = book
         return book
 
-    def forward(self, inp):
+    def _bf16_train(self, inp):
+        """Does this call run on the bf16 training kernels?  bf16 sparse mode, gradients wanted, device features, and not the
+        narrow first layer (Cin < 16: voxel means in metres stay fp32)."""
+        f = inp.features
+        return (AG.sparse_precision() == "bf16" and torch.is_grad_enabled() and f.is_cuda and self.in_channels >= 16
+                and (inp._carrier is not None or f.requires_grad or self.weight.requires_grad))
+
+    def _forward_bf16(self, inp, bn):
+        """bf16 training path: conv (+ the BatchNorm1d + ReLU that follow, `bn`, as one autograd node).  A layer shape without
+        bf16 kernels is an error, never a silent fp32 layer."""
+        cin, cout = self.in_channels, self.out_channels
+        n = inp.indices.shape[0]
+        if self.conv1x1:
+            k, nbr, out_idx, oshape, otable, n_out = 1, None, inp.indices, inp.spatial_shape, inp._table, n
+        else:
+            out_idx, nbr, oshape, otable = self.book(inp)
+            k, n_out = 27, out_idx.shape[0]
+            if self.subm:
+                otable = inp._table
+        cap = max(n_out, n, 1) if nbr is None else max(nbr.shape[0], n, 1)
+        if not AG.sparse_bf16_layer_supported(k, cin, cout, cap):
+            raise ValueError("sparse_precision='bf16': no bf16 training kernels for sparse conv %s (%d -> %d, kernel %s, %d rows)"
+                             % (self.indice_key or type(self).__name__, cin, cout, "x".join(map(str, self.kernel_size)), cap))
+        if inp._carrier is not None:
+            carrier, xb = inp._carrier, inp.features
+        else:                                         # fp32 features enter the bf16 trunk: rounded once (nearest even)
+            carrier = inp.features.contiguous().float()
+            xb = carrier.detach().to(torch.bfloat16)
+        w = self.weight.view(k, cin, cout)
+        subm = isinstance(self, SubMConv3d)
+        out = SparseConvTensor(None, out_idx, oshape, inp.batch_size)
+        out.indice_dict, out._table = inp.indice_dict, otable
+        if bn is not None and self.bias is None and n_out > 0:
+            out._carrier, out.features = AG.SparseConvBnReluBf16Fn.apply(carrier, xb, w, nbr, n_out, subm, bn.weight, bn.bias,
+                                                                        bn.running_mean, bn.running_var, bn.momentum, bn.eps)
+            count_bn_batch(bn)
+            out._bn_fused = True
+        else:
+            y = AG.SparseConvBf16Fn.apply(carrier, xb, w, nbr, n_out, subm)
+            out.features = y + self.bias if self.bias is not None else y
+        return out
+
+    def forward(self, inp, bn=None):
+        """bn: the training-mode BatchNorm1d (+ ReLU) that follows this layer in a SparseSequential; only the bf16 training path
+        fuses it (the result then carries `_bn_fused`)."""
         assert isinstance(inp, SparseConvTensor)
-        feats = inp.features.contiguous().float()
+        if self._bf16_train(inp):
+            return self._forward_bf16(inp, bn)
+        feats = inp.features_f32().contiguous().float()
         n = inp.indices.shape[0]
         grad = torch.is_grad_enabled() and (feats.requires_grad or self.weight.requires_grad)
         if self.conv1x1:
@@ -170,13 +227,26 @@ class SparseSequential(nn.Sequential):
     # 2e-5 / 1e-4).  Set to False for torch's own BatchNorm1d + ReLU (A/B, bench.py --torch-bn).
     fuse_bn_relu = True
 
+    def _fusable_bn(self, m, nxt, channels):
+        return (self.fuse_bn_relu and isinstance(m, nn.BatchNorm1d) and isinstance(nxt, nn.ReLU) and m.training
+                and m.affine and m.track_running_stats and m.momentum is not None and torch.is_grad_enabled()
+                and K.bn_relu_supported(1, channels))
+
     def forward(self, inp):
         mods = list(self)
         i = 0
         while i < len(mods):
             m = mods[i]
             if isinstance(m, SparseConvolution):
-                inp = m(inp)
+                if AG.sparse_precision() == "bf16" and m._bf16_train(inp):
+                    # bf16 sparse training: conv + BatchNorm1d + ReLU are one autograd node (SparseConvBnReluBf16Fn)
+                    bn = mods[i + 1] if i + 2 < len(mods) and self._fusable_bn(mods[i + 1], mods[i + 2], m.out_channels) else None
+                    inp = m(inp, bn)
+                    if getattr(inp, "_bn_fused", False):
+                        i += 3
+                        continue
+                else:
+                    inp = m(inp)
             elif isinstance(inp, SparseConvTensor):
                 if inp.indices.shape[0] != 0:
                     f = inp.features
@@ -185,11 +255,18 @@ class SparseSequential(nn.Sequential):
                             and m.affine and m.track_running_stats and m.momentum is not None and f.is_cuda
                             and f.dtype == torch.float32 and torch.is_grad_enabled()
                             and K.bn_relu_supported(f.shape[0], f.shape[1])):
-                        inp.features = BnReluFn.apply(f, m.weight, m.bias, m.running_mean, m.running_var, m.momentum,
-                                                      m.eps)
+                        if AG.sparse_precision() == "bf16":
+                            # behind an fp32 conv (the first layer): the same BatchNorm + ReLU, stored bf16 for the next conv
+                            inp._carrier, inp.features = AG.BnReluBf16OutFn.apply(f, m.weight, m.bias, m.running_mean,
+                                                                                  m.running_var, m.momentum, m.eps)
+                        else:
+                            inp.features = BnReluFn.apply(f, m.weight, m.bias, m.running_mean, m.running_var, m.momentum,
+                                                          m.eps)
                         count_bn_batch(m)
                         i += 2
                         continue
+                    if inp._carrier is not None:              # a plain module on bf16 training features: widened exactly
+                        f, inp._carrier = inp.features_f32(), None
                     inp.features = m(f)
             else:
                 inp = m(inp)

@@ -88,7 +88,7 @@ class PackPlan:
 
     def __init__(self, model, flat):
         import numpy as np
-        from .autograd import SparseConvFn, bev_precision, bf16_cout_pad
+        from .autograd import SparseConvFn, bev_precision, bf16_cout_pad, sparse_bf16_layer_supported, sparse_precision
         from .detector import _HipConv2d
         from .spconv import SparseConvolution, SubMConv3d
         self.flat = flat
@@ -140,10 +140,31 @@ class PackPlan:
             assert idx.size == _C.lib().sassd_conv1x1_bf16_packed_elems(ci_n, co_n)
             return torch.from_numpy(idx.reshape(-1).astype(np.int32)).to(dev)
 
+        def sp16_map(off, k, cin, cout, kind):
+            """gather maps of the bf16 sparse images (autograd._spconv16_pack): [K][Cout][Cin] of the forward weight; the data
+            gradient's image of W[k]^T is the weight's own [K][Cin][Cout] order, offsets reversed for the forward-table form"""
+            i = off + np.arange(k * cin * cout, dtype=np.int64).reshape(k, cin, cout)
+            i = i.transpose(0, 2, 1) if kind == "spconv16" else (i[::-1] if kind == "spconv16_t_rev" else i)
+            return torch.from_numpy(np.ascontiguousarray(i).reshape(-1).astype(np.int32)).to(dev)
+
+        def add_aligned(maps, sinks, m, weight, kind):
+            """add() on a 16-byte boundary of the bf16 output (the sparse kernels load their image in 16-byte pieces)"""
+            pad = -sum(x.numel() for x in maps) % 8
+            if pad:
+                maps.append(torch.full((pad,), -1, dtype=torch.int32, device=dev))
+            add(maps, sinks, m, weight, kind)
+
         bf16 = bev_precision() == "bf16"
+        # the bf16 sparse images: with the setter on, or a detector whose train_cfg asks for the mode
+        sp16 = (getattr(model, "train_cfg", None) or {}).get("sparse_precision") or sparse_precision()
         for m in model.modules():
             if isinstance(m, SparseConvolution) and m.weight.requires_grad:
                 k = int(np.prod(m.kernel_size))
+                if sp16 == "bf16" and m.in_channels >= 16 and sparse_bf16_layer_supported(k, m.in_channels, m.out_channels, 1):
+                    off = (m.weight.data_ptr() - base) // 4
+                    rev = isinstance(m, SubMConv3d) and k == 27 and SparseConvFn.subm_on_forward_table
+                    for kind in ("spconv16", "spconv16_t_rev" if rev else "spconv16_t"):
+                        add_aligned(bf_maps, self._bf, sp16_map(off, k, m.in_channels, m.out_channels, kind), m.weight, kind)
                 wi = bits(idx_like(m.weight).reshape(k, m.in_channels, m.out_channels))
                 add_f32(K.spconv_pack_weight(wi), m.weight, "spconv")
                 if m.in_channels >= 16:

@@ -8,7 +8,8 @@ weight: MFMA-fragment packs, Winograd G g G^T, bf16 packs and the transposed / t
 
 One rule for every kind:
 
-  * key (address, numel, kind) + extra.  `kind` names the layout ("spconv", "spconv_t", "spconv_t_rev", "direct", "wino2",
+  * key (address, numel, kind) + extra.  `kind` names the layout ("spconv", "spconv_t", "spconv_t_rev", "spconv16", "spconv16_t",
+    "spconv16_t_rev", "direct", "wino2",
     "wino4", "dgrad", "bf16_3x3", "bf16_3x3_t", "bf16_1x1", "bf16_1x1_t"); `extra` carries (h, w) where the FORM of the image
     depends on the map size (the fp32 data-gradient image of a 3x3 layer).
   * an entry is valid while kernels.weight_key(weight) -- version counter, address, device, global generation -- equals the
