@@ -35,6 +35,7 @@ extern "C" {
 #define SASSD_ST_HASH_FULL        2   /* hash table probe exhausted             */
 #define SASSD_ST_BOX_OVERFLOW     4   /* more candidate boxes than capK / capD  */
 #define SASSD_ST_GRID_SYNC        8   /* an in-launch grid barrier timed out (persistent rulebook pyramid) */
+#define SASSD_ST_POINT_OVERFLOW  16   /* more points than a point capacity (sassd_crop_polytope_dev) */
 
 #define SASSD_MAX_POINTS_PER_VOXEL 64  /* max_points supported by sassd_voxelize (reference default: 35) */
 
@@ -102,6 +103,38 @@ int sassd_voxelize_dev(const float *points, int points_cap, const int32_t *n_poi
 /* SimpleVoxel.forward alone (vxnet.py:110-116): mean[v,f] = sum_t voxels[v,t,f] / num_points[v]. */
 int sassd_voxel_mean(const float *voxels, const int32_t *num_points, int m, int max_points, int ndim,
                      int nfeat, float *mean, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Frustum crop: the FIRST nodes of a captured frame that starts at a raw 360-degree sweep.  Stable compaction of a point
+ * cloud to one convex polytope -- the camera-2 viewing frustum of `remove_outside_points` (geometry.py:50-61, the
+ * velodyne -> velodyne_reduced step of tools/create_data.py) -- with the point count in device memory on both sides, so
+ * that sassd_voxelize_dev can follow it in the same graph.
+ *
+ * CONTRACT
+ *   points     [cap_in, ndim] f32 device (ndim >= 3, xyz first);  n = min(*n_in_dev, cap_in) rows are the cloud (a
+ *              negative count reads as 0).  Nothing is read past cap_in rows.
+ *   planes     [6][4] f64 device: (nx, ny, nz, d) per face, as sassd_points_in_polytopes takes them; f32_math likewise.
+ *   kept       row i < n is kept iff no face gives n.p + d >= 0 (a point ON a face is outside) -- the same device
+ *              function sassd_points_in_polytopes evaluates (inside_polytope, csrc/augment_core.h: float64, or float32
+ *              with f32_math, products and sums rounded separately).
+ *   out        [cap_out, ndim] f32 device: the kept rows in ASCENDING i (stable), all ndim floats copied bit for bit.
+ *              *n_out_dev = min(kept, cap_out); rows of `out` at and beyond *n_out_dev are not written.
+ *   overflow   kept > cap_out: the first cap_out kept rows are written and SASSD_ST_POINT_OVERFLOW is OR-ed into *status.
+ *              The same flag is set when *n_in_dev > cap_in.  `status` is only ever OR-ed into.
+ *   workspace  sassd_crop_polytope_workspace_bytes(cap_in) bytes, 4-byte aligned: one int32 count per 256 rows of
+ *              cap_in.  Every count is rewritten by every call (a replay with a smaller n sees no stale count).
+ *   launches   two kernels, a grid of ceil(cap_in / 1024) workgroups each (one for cap_in == 0): the shape depends on
+ *              cap_in only.  No host sync, no allocation, no memset, no atomics but the OR into `status`, and no
+ *              workgroup waits for another inside a launch.  ndim == 4 with 16-byte aligned points / out moves rows as
+ *              16-byte vectors; any other ndim (or alignment) takes a strided path with the same result.
+ *   errors     SASSD_EINVAL before any HIP call: a NULL pointer (every pointer is required), ndim < 3, cap_in < 0,
+ *              cap_out < 1, planes not 8-byte aligned, points / out / workspace not 4-byte aligned, workspace_bytes
+ *              below the query.
+ * ---------------------------------------------------------------------------------------------- */
+size_t sassd_crop_polytope_workspace_bytes(int cap_in);
+int sassd_crop_polytope_dev(const float *points, int cap_in, const int32_t *n_in_dev, int ndim,
+                            const double *planes, int f32_math, float *out, int cap_out, int32_t *n_out_dev,
+                            int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * (a5) Rulebook build.  Replaces spconv v1.0 `get_indice_pairs` as invoked by SubMConv3d / SparseConv3d

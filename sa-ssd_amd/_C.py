@@ -12,6 +12,7 @@ _lib = None
 
 OK, EINVAL, ENOSPC, EHIP = 0, -1, -2, -3
 ST_VOXEL_OVERFLOW, ST_HASH_FULL, ST_BOX_OVERFLOW = 1, 2, 4
+ST_POINT_OVERFLOW = 16
 
 
 def build(force=False, verbose=False):
@@ -40,6 +41,9 @@ _SIGS = {
     "sassd_voxelize": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _SZ, _P]),
     "sassd_voxelize_dev": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _SZ, _P]),
     "sassd_voxel_mean": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    # frustum crop (include/sassd.h "Frustum crop")
+    "sassd_crop_polytope_workspace_bytes": (_SZ, [_I]),
+    "sassd_crop_polytope_dev": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _SZ, _P]),
     "sassd_hash_bytes": (_SZ, [_I]),
     "sassd_hash_build": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P, _P]),
     "sassd_rulebook_subm": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P, _P]),

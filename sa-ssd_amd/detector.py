@@ -992,11 +992,13 @@ class SingleStageDetector(nn.Module):
                 out.append(dict(boxes_lidar=boxes, scores=scores, labels=labels))
         return out
 
-    def frame_stream(self, anchors, inflight=3, points_cap=None, batch_size=1, device=None, **kw):
+    def frame_stream(self, anchors, inflight=3, points_cap=None, batch_size=1, device=None, raw_cap=None, **kw):
         """A sassd.stream.FrameStream over this model's weights: raw point clouds in, `inflight` frames in flight, the
         detections of plan.results() out, in order.  Thresholds and precisions come from test_cfg the way plan() takes them
         (score_thr, nms.iou_thr; precision / sparse_precision unless given); the voxelizer's settings and anything else
-        InferencePlan accepts go through **kw.  The stream holds a copy of the weights as they are now."""
+        InferencePlan accepts go through **kw.  The stream holds a copy of the weights as they are now.  `raw_cap`: the stream
+        takes raw sweeps of up to that many points and crops each to its camera frustum inside the frame
+        (FrameStream(raw_cap=...): submit(clouds, frustums))."""
         from .stream import FrameStream
         precision = kw.pop('precision', None) or ((self.test_cfg or {}).get('precision') or 'fp32')
         sparse_precision = kw.pop('sparse_precision', None) or ((self.test_cfg or {}).get('sparse_precision') or 'fp32')
@@ -1007,8 +1009,8 @@ class SingleStageDetector(nn.Module):
             device = next(self.parameters()).device
         an = anchors.detach().cpu().numpy() if torch.is_tensor(anchors) else np.asarray(anchors)
         return FrameStream(self.state_dict(), inflight=inflight, points_cap=points_cap, batch_size=batch_size,
-                           anchors=an.reshape(-1, 7), device=device, precision=precision, sparse_precision=sparse_precision,
-                           **dict(self._cfg, **kw))
+                           anchors=an.reshape(-1, 7), device=device, raw_cap=raw_cap, precision=precision,
+                           sparse_precision=sparse_precision, **dict(self._cfg, **kw))
 
     def forward(self, img, img_meta, return_loss=True, **kwargs):
         if return_loss:

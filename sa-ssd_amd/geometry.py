@@ -210,10 +210,19 @@ def points_in_rbbox(points, rbbox, lidar=True, device=None):
                                            device=device)
 
 
+def frustum_planes(rect, Trv2c, P2, image_shape):
+    """The camera-2 viewing frustum of an image of shape (h, w) as ([6,4] float64 (nx, ny, nz, d), f32_math): the planes
+    `remove_outside_points` tests against, for sassd_crop_polytope_dev (kernels.crop_polytope, FrameStream(raw_cap=...)).
+    Host arithmetic only: it needs no GPU."""
+    frustum = frustum_in_lidar(rect, Trv2c, P2, image_shape)
+    planes, f32 = planes_of_surfaces(corner_to_surfaces_3d(frustum[np.newaxis, ...]))
+    return planes[0], f32
+
+
 def remove_outside_points(points, rect, Trv2c, P2, image_shape, device=None):
     """keep the points inside the camera-2 viewing frustum (velodyne -> velodyne_reduced)."""
-    frustum = frustum_in_lidar(rect, Trv2c, P2, image_shape)
-    keep = points_in_convex_polygon_3d_jit(points, corner_to_surfaces_3d(frustum[np.newaxis, ...]), device=device)
+    planes, f32 = frustum_planes(rect, Trv2c, P2, image_shape)
+    keep = points_in_polytopes(points[:, :3] if not torch.is_tensor(points) else points, planes[np.newaxis], f32, device)
     return points[keep.reshape([-1])]
 
 

@@ -116,6 +116,35 @@ def voxelize(points, voxel_size, coors_range, max_points, max_voxels, batch_idx=
     return dict(voxels=voxels, coors=coors, num_points=num, mean=mean, voxel_num=vnum)
 
 
+def crop_polytope(points, n_in, planes, f32_math, out, n_out, status):
+    """Stable compaction of a staged cloud to one convex polytope (include/sassd.h "Frustum crop"): the first
+    min(n_in, cap_in) rows of `points` [cap_in, ndim] f32 that lie inside `planes` ([6,4] f64 device) go to `out`
+    [cap_out, ndim] f32 in their order, their number to `n_out`; `n_in` / `n_out` / `status` are device int32 scalars.
+    Two kernel launches whose shape depends on cap_in only (graph-capturable); the workspace is the scoped one."""
+    _chk_cuda(points, n_in, planes, out, n_out, status)
+    if points.dim() != 2 or out.dim() != 2 or points.shape[1] != out.shape[1] or points.shape[1] < 3:
+        raise ValueError("crop_polytope: points %s and out %s must be [rows, ndim >= 3] with one ndim"
+                         % (tuple(points.shape), tuple(out.shape)))
+    if points.dtype != torch.float32 or out.dtype != torch.float32:
+        raise ValueError("crop_polytope: points and out must be float32")
+    if planes.dtype != torch.float64 or tuple(planes.shape) != (6, 4):
+        raise ValueError("crop_polytope: planes must be [6, 4] float64, got %s %s" % (tuple(planes.shape), planes.dtype))
+    for name, t in (("n_in", n_in), ("n_out", n_out), ("status", status)):
+        if t.dtype != torch.int32 or t.numel() != 1:
+            raise ValueError("crop_polytope: %s must be one int32 word" % name)
+    if out.shape[0] < 1:
+        raise ValueError("crop_polytope: out needs at least one row")
+    L = _C.lib()
+    cap_in, ndim = int(points.shape[0]), int(points.shape[1])
+    wsb = L.sassd_crop_polytope_workspace_bytes(cap_in)
+    ws = workspace("crop_polytope", wsb, points.device)
+    rc = L.sassd_crop_polytope_dev(_C.ptr(points), cap_in, _C.ptr(n_in), ndim, _C.ptr(planes), int(bool(f32_math)),
+                                   _C.ptr(out), int(out.shape[0]), _C.ptr(n_out), _C.ptr(status), _C.ptr(ws), wsb,
+                                   _C.stream())
+    _C.check(rc, "sassd_crop_polytope_dev")
+    return out, n_out
+
+
 def voxel_mean(voxels, num_points, nfeat=4):
     _chk_cuda(voxels, num_points)
     m, t, ndim = voxels.shape

@@ -106,9 +106,10 @@ class KittiLiDAR:
         w, h = self.img_scales[0]
         return (h, w, 3)
 
-    def load_frame(self, idx, with_label=True):
+    def load_frame(self, idx, with_label=True, lidar_prefix=None):
         """Everything the files hold for sample idx: dict(sample_idx, img_shape, calib, points [N,4] f32 numpy,
-        gt_bboxes [G,7] f32 lidar frame, gt_types list, plane)."""
+        gt_bboxes [G,7] f32 lidar frame, gt_types list, plane).  `lidar_prefix`: read the points from that directory
+        instead of self.lidar_prefix (raw sweeps: runner.single_test(raw_prefix=...))."""
         sample_id = self.sample_ids[idx]
         calib = Calibration(osp.join(self.calib_prefix, '%06d.txt' % sample_id))
         out = dict(sample_idx=sample_id, img_shape=self.image_shape(sample_id), calib=calib, plane=None)
@@ -118,7 +119,7 @@ class KittiLiDAR:
                 boxes[:, :3] = project_rect_to_velo(boxes[:, :3], calib)      # camera -> lidar (kitti.py:152-154)
             out.update(gt_bboxes=boxes, gt_types=types)
         if self.with_point:
-            out['points'] = read_lidar(osp.join(self.lidar_prefix, '%06d.bin' % sample_id))
+            out['points'] = read_lidar(osp.join(lidar_prefix or self.lidar_prefix, '%06d.bin' % sample_id))
         if self.with_plane:
             out['plane'] = get_road_plane(osp.join(self.plane_prefix, '%06d.txt' % sample_id))
         return out

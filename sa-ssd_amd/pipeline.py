@@ -651,7 +651,7 @@ class InferencePlan:
             return self._tail(anchors_mask)
 
     # ---- hipGraph: the whole frame as ONE launch ---------------------------------------------------------
-    def capture(self, points_cap, ndim=4, stages=("voxelize", "backbone", "tail"), seal=False):
+    def capture(self, points_cap, ndim=4, stages=("voxelize", "backbone", "tail"), seal=False, raw_cap=None):
         """Capture the frame (raw points -> detections, side stream included) into a hipGraph.  Input staging:
         `self.pts_in[b]` [points_cap, ndim] f32 and `self.npts` int32 [B]; `run_graph(clouds)` fills them and replays.
         `stages` lets a caller capture a sub-range (e.g. only the sparse backbone for a roofline measurement).
@@ -659,20 +659,48 @@ class InferencePlan:
         include/sassd.h after every replay, its `seq` word echoed from a device word, which shares one int32 block
         [seq, npts[B]] with `self.npts` so that both are staged in one copy (sassd.stream.FrameStream).
         The launch sequence that was captured stays on the plan as `_frame_fn`, for inspection only (a test captures it once
-        more into a plain hipGraph to count its node types); nothing on the frame path calls it."""
+        more into a plain hipGraph to count its node types); nothing on the frame path calls it.
+        raw_cap: the frame starts at a raw sweep.  Its input is `self.raw_in[b]` [raw_cap, ndim] f32, `self.nraw` int32 [B] and
+        `self.crop_planes` [B,6,4] f64 (`self.crop_f32_math`, a host flag read at capture, says how they are evaluated:
+        False, the float64 test of geometry.frustum_planes); its first nodes are one sassd_crop_polytope_dev per sample
+        (two kernels each), which write `pts_in[b]` and `npts[b]` for the unchanged voxelizer.  A sweep that keeps more than
+        points_cap points sets SASSD_ST_POINT_OVERFLOW.  Staging: planes and counts share ONE device block `_stage_block`
+        (uint8: [B,6,4] f64 planes first, so they are 8-byte aligned, then the int32 words [seq, nraw[B]] when sealed, else
+        [nraw[B]]), so a frame's small inputs still travel in one copy (sassd.stream.FrameStream)."""
         dev = self.dev
         self.pts_cap = int(points_cap)
+        self.raw_cap = None if raw_cap is None else int(raw_cap)
+        if self.raw_cap is not None and (self.raw_cap < 1 or "voxelize" not in stages):
+            raise ValueError("raw_cap must be >= 1 and needs the voxelize stage")
         self.pts_in = [torch.zeros(self.pts_cap, ndim, dtype=torch.float32, device=dev) for _ in range(self.B)]
-        if seal:
+        if self.raw_cap is not None:
+            self.raw_in = [torch.zeros(self.raw_cap, ndim, dtype=torch.float32, device=dev) for _ in range(self.B)]
+            nplane = self.B * 6 * 4 * 8
+            self._stage_block = torch.zeros(nplane + 4 * (self.B + (1 if seal else 0)), dtype=torch.uint8, device=dev)
+            self.crop_planes = self._stage_block[:nplane].view(torch.float64).view(self.B, 6, 4)
+            self.crop_f32_math = False
+            words = self._stage_block[nplane:].view(torch.int32)
+            self.npts = torch.zeros(self.B, dtype=torch.int32, device=dev)      # written by the crop, read by the voxelizer
+            if seal:
+                self._stage_words = words
+                self._seq, self.nraw = words[:1], words[1:]
+            else:
+                self.nraw = words
+        elif seal:
             self._stage_words = torch.zeros(1 + self.B, dtype=torch.int32, device=dev)
             self._seq, self.npts = self._stage_words[:1], self._stage_words[1:]
-            self.record = torch.zeros(K.frame_record_bytes(self.B, self.capD), dtype=torch.uint8, device=dev)
         else:
             self.npts = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        if seal:
+            self.record = torch.zeros(K.frame_record_bytes(self.B, self.capD), dtype=torch.uint8, device=dev)
         assert self.prof is None, "per-stage event timing and graph capture exclude each other"
 
         def frame():
             with K.ws_scope(self._wsid):
+                if self.raw_cap is not None:
+                    for b in range(self.B):
+                        K.crop_polytope(self.raw_in[b], self.nraw[b:b + 1], self.crop_planes[b], self.crop_f32_math,
+                                        self.pts_in[b], self.npts[b:b + 1], self.status)
                 if "voxelize" in stages:
                     self.voxelize(self.pts_in, n_dev=self.npts)
                 if "backbone" in stages:
@@ -705,6 +733,8 @@ class InferencePlan:
         return self.graph
 
     def stage_inputs(self, clouds):
+        if getattr(self, "raw_cap", None) is not None:
+            raise RuntimeError("a plan captured with raw_cap is fed through raw_in / nraw / crop_planes (sassd.stream.FrameStream)")
         for b, pts in enumerate(clouds or ()):
             n = pts.shape[0]
             if n > self.pts_cap:            # never detect on a silently truncated cloud

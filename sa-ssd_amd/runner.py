@@ -59,12 +59,18 @@ def train_model(model, optimizer, train_loader, lr_scheduler, sync, start_epoch,
 
 
 def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=None, world=None, inflight=0,
-                points_cap=None):
+                points_cap=None, raw_prefix=None):
     """Run the detector over `dataset` (test mode) -> list of KITTI result annotations in dataset order on every rank
     (this rank's frames are computed here, the others' gathered from their ranks).  `saveto`: also write result files.
     inflight > 0: the frames' raw points go through model.frame_stream(...) with that many frames in flight (1..4) instead of
     collate + model(...): same annotations, the voxelizer and the anchor mask inside the captured frame.  `points_cap`: the
-    largest cloud of the stream (default: from the sizes of this rank's point files)."""
+    largest cloud of the stream (default: from the sizes of this rank's point files).
+    `raw_prefix` (with inflight > 0): a directory of RAW sweeps (%06d.bin, [N,4] f32 -- KITTI's velodyne/) read instead of
+    dataset.lidar_prefix; the stream is built with raw_cap (the largest file, rounded up to 1024 points) and crops every
+    sweep to the camera frustum of its own calib and img_shape inside the captured frame, so the annotations are those of
+    the velodyne_reduced/ files.  points_cap (the most points a frustum may keep) then defaults to raw_cap: always enough,
+    but the voxelizer's tables are sized for a whole sweep -- pass the real bound (KITTI: about a fifth of the sweep) to
+    keep the frame's memory and its fill kernels at the size of the reduced path."""
     if rank is None or world is None:
         rank, _, world = D.env_world() if D.dist.is_initialized() else (0, 0, 1)
     if class_names is not None:
@@ -74,7 +80,9 @@ def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=N
     annos = []
     with torch.no_grad():
         if inflight:
-            annos = _stream_test(model, dataset, mine, workers, inflight, points_cap)
+            annos = _stream_test(model, dataset, mine, workers, inflight, points_cap, raw_prefix)
+        elif raw_prefix is not None:
+            raise ValueError("raw_prefix needs inflight > 0 (the crop lives in the captured frame of a FrameStream)")
         else:
             for batch in FrameLoader(dataset, 1, sampler=mine, num_workers=workers):
                 annos += model(**batch)
@@ -87,7 +95,7 @@ def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=N
     return merged
 
 
-def _stream_test(model, dataset, indices, workers, inflight, points_cap=None):
+def _stream_test(model, dataset, indices, workers, inflight, points_cap=None, raw_prefix=None):
     """single_test's frames through a FrameStream: the point files are read ahead on `workers` threads, submitted as host
     clouds, and every result becomes the annotation forward_test builds for the frame's img_meta."""
     from concurrent.futures import ThreadPoolExecutor
@@ -96,13 +104,22 @@ def _stream_test(model, dataset, indices, workers, inflight, points_cap=None):
     indices = [int(i) for i in indices]
     if not indices:
         return []
-    if points_cap is None:                      # the files load_frame reads: [N, 4] float32 (kitti_common.read_lidar)
-        sizes = [os.path.getsize(os.path.join(dataset.lidar_prefix, '%06d.bin' % dataset.sample_ids[i])) for i in indices]
+    prefix = dataset.lidar_prefix if raw_prefix is None else raw_prefix
+    raw_cap = None
+    if points_cap is None or raw_prefix is not None:    # the files read below: [N, 4] float32 (kitti_common.read_lidar)
+        sizes = [os.path.getsize(os.path.join(prefix, '%06d.bin' % dataset.sample_ids[i])) for i in indices]
         if any(n % 16 for n in sizes):
-            raise ValueError("a point file under %s is not a whole number of 16-byte points: pass points_cap" % dataset.lidar_prefix)
-        points_cap = (max(sizes) // 16 + 1023) // 1024 * 1024 or 1024      # rounded up to 1024 points
+            raise ValueError("a point file under %s is not a whole number of 16-byte points%s"
+                             % (prefix, "" if raw_prefix is not None else ": pass points_cap"))
+        file_cap = (max(sizes) // 16 + 1023) // 1024 * 1024 or 1024        # rounded up to 1024 points
+        if raw_prefix is not None:
+            raw_cap = file_cap
+        if points_cap is None:
+            points_cap = file_cap
+    load = (dataset.load_frame, False) if raw_prefix is None else (dataset.load_frame, False, raw_prefix)
     gen = dataset.generator
     fs = model.frame_stream(dataset.anchors, inflight=inflight, points_cap=points_cap, batch_size=1, device=dataset._dev(),
+                            **({} if raw_cap is None else dict(raw_cap=raw_cap)),
                             anchors_bv=dataset.anchors_bv, voxel_size=tuple(gen.voxel_size),
                             point_cloud_range=tuple(gen.point_cloud_range), max_num_points=gen.max_num_points_per_voxel,
                             max_voxels=gen._max_voxels, anchor_area_threshold=dataset.anchor_area_threshold)
@@ -111,15 +128,18 @@ def _stream_test(model, dataset, indices, workers, inflight, points_cap=None):
         with ThreadPoolExecutor(max(1, int(workers))) as pool:
             def batches():
                 ahead = max(1, int(workers)) + inflight
-                pending = deque(pool.submit(dataset.load_frame, i, False) for i in indices[:ahead])
+                pending = deque(pool.submit(load[0], i, *load[1:]) for i in indices[:ahead])
                 nxt = len(pending)
                 while pending:
                     fr = pending.popleft().result()
                     if nxt < len(indices):
-                        pending.append(pool.submit(dataset.load_frame, indices[nxt], False))
+                        pending.append(pool.submit(load[0], indices[nxt], *load[1:]))
                         nxt += 1
                     metas.append(dict(img_shape=fr['img_shape'], sample_idx=fr['sample_idx'], calib=fr['calib']))
-                    yield [fr['points']]
+                    if raw_prefix is None:
+                        yield [fr['points']]
+                    else:
+                        yield [fr['points']], [dict(calib=fr['calib'], img_shape=fr['img_shape'])]
             for _, dets in fs.map(batches()):
                 annos += model.result_annos(dets, [metas.popleft()])
     finally:

@@ -17,6 +17,11 @@ stage / launch / ready / wait / record -- the CPU tests hand it a fake one.
     for ticket, dets in fs.map(batches):     # dets: what plan.results() returns for that batch
         ...
     fs.close()
+
+Raw sweeps: FrameStream(..., raw_cap=122880) puts the camera-frustum reduction (velodyne -> velodyne_reduced) into the
+captured frame -- sassd_crop_polytope_dev, two kernels per sample in front of the voxelizer.  submit(clouds, frustums) then
+takes clouds of up to raw_cap points and one frustum per cloud ([6,4] float64 planes of geometry.frustum_planes, or
+dict(calib=..., img_shape=...)); the planes ride in the staging block of the counts: [planes[B,6,4] f64 | seq, nraw[B]].
 """
 from collections import deque
 
@@ -55,6 +60,75 @@ def status_error(st):
     return FrameStatusError(st)
 
 
+def _extend4(m):
+    """3x3 / 3x4 / 4x4 calibration matrix -> 4x4 float64, padded as kitti_common.get_kitti_image_info(extend_matrix=True)."""
+    m = np.asarray(m, dtype=np.float64)
+    if m.shape == (4, 4):
+        return m
+    out = np.zeros((4, 4))
+    out[3, 3] = 1.
+    out[:m.shape[0], :m.shape[1]] = m
+    return out
+
+
+def frustum_of(calib, img_shape):
+    """The [6,4] float64 planes of a frame's camera-2 viewing frustum (geometry.frustum_planes) from its calibration -- a
+    kitti_common.Calibration (P2, R0, V2C) or a dict with P2, R0_rect, Tr_velo_to_cam (3x3 / 3x4 / 4x4, or the flat rows
+    of a KITTI calib file) -- and its image shape (h, w).  Host arithmetic only."""
+    from .geometry import frustum_planes
+    if isinstance(calib, dict):
+        get = lambda *ks: next(calib[k] for k in ks if k in calib)      # noqa: E731
+        p2, r0, v2c = get("P2", "calib/P2"), get("R0_rect", "calib/R0_rect"), get("Tr_velo_to_cam", "calib/Tr_velo_to_cam")
+    else:
+        p2, r0, v2c = calib.P2, calib.R0, calib.V2C
+    p2, r0, v2c = (np.asarray(m, dtype=np.float64) for m in (p2, r0, v2c))
+    if p2.ndim == 1:
+        p2 = p2.reshape(3, 4)
+    if r0.ndim == 1:
+        r0 = r0.reshape(3, 3)
+    if v2c.ndim == 1:
+        v2c = v2c.reshape(3, 4)
+    planes, f32 = frustum_planes(_extend4(r0), _extend4(v2c), _extend4(p2), (int(img_shape[0]), int(img_shape[1])))
+    assert not f32                                  # float64 calibration gives float64 planes: the stream's crop is float64
+    return planes
+
+
+def check_frame_inputs(clouds, frustums, B, ndim, points_cap, raw_cap=None):
+    """The checks a slot makes on one frame's inputs before it queues anything (host only).  ValueError for: the wrong
+    number of clouds, a cloud that is not [N, ndim], a cloud above the stream's capacity (raw_cap on a raw stream, else
+    points_cap), frustums missing on a raw stream or given to a stream without raw_cap, the wrong number of frustums,
+    planes that are not [6,4] or not finite.  -> the planes as one [B,6,4] float64 array, or None without raw_cap."""
+    if len(clouds) != B:
+        raise ValueError("a batch of %d clouds for a stream of batch_size %d" % (len(clouds), B))
+    cap, what = (points_cap, "points_cap") if raw_cap is None else (raw_cap, "raw_cap")
+    for b, pts in enumerate(clouds):        # never detect on a silently truncated cloud
+        if pts.ndim != 2 or pts.shape[1] != ndim:
+            raise ValueError("cloud %d has shape %s, expected [N, %d]" % (b, tuple(pts.shape), ndim))
+        if pts.shape[0] > cap:
+            raise ValueError("cloud %d has %d points, the stream was sized for %d (%s)" % (b, pts.shape[0], cap, what))
+    if raw_cap is None:
+        if frustums is not None:
+            raise ValueError("frustums given to a stream without raw_cap (its clouds are taken as they are)")
+        return None
+    if frustums is None:
+        raise ValueError("a stream with raw_cap crops every cloud: submit(clouds, frustums) needs one frustum per cloud")
+    if len(frustums) != B:
+        raise ValueError("%d frustums for a stream of batch_size %d" % (len(frustums), B))
+    out = np.empty((B, 6, 4), dtype=np.float64)
+    for b, f in enumerate(frustums):
+        if isinstance(f, dict):
+            if "calib" not in f or "img_shape" not in f:
+                raise ValueError("frustum %d: a dict needs `calib` and `img_shape`" % b)
+            f = frustum_of(f["calib"], f["img_shape"])
+        f = np.asarray(f)
+        if f.shape != (6, 4) or f.dtype != np.float64:
+            raise ValueError("frustum %d: planes must be a [6, 4] float64 array, got %s %s" % (b, f.shape, f.dtype))
+        if not np.isfinite(f).all():
+            raise ValueError("frustum %d: planes must be finite" % b)
+        out[b] = f
+    return out
+
+
 def decode_record(buf, B, capD, seq):
     """One frame record (bytes-like / uint8 array of record_layout(B, capD)['total'] bytes) -> what plan.results() returns:
     per sample (boxes [k,7] f32, scores [k] f32, labels [k] i64), or (None, None, None) for a sample without detections.
@@ -89,7 +163,8 @@ def decode_record(buf, B, capD, seq):
 class FrameRing:
     """Tickets over a ring of slots.  Ticket t (1, 2, ...) runs on slot (t - 1) % len(slots); a slot is
 
-        stage(seq, clouds)   check and queue the inputs of one frame (ValueError for inputs it cannot take: nothing queued)
+        stage(seq, clouds)   check and queue the inputs of one frame (ValueError for inputs it cannot take: nothing queued);
+                             called as stage(seq, clouds, frustums) when submit() was given frustums, and only then
         launch()             queue the frame and the copy of its record
         ready() / wait()     has the record arrived / block until it has
         record()             the arrived record, valid until the next stage()
@@ -124,14 +199,17 @@ class FrameRing:
                 recover()
         self.busy[i] = None
 
-    def submit(self, clouds):
+    def submit(self, clouds, frustums=None):
         if self.closed:
             raise RuntimeError("FrameStream is closed")
         t = self.next_ticket
         i = (t - 1) % len(self.slots)
         if self.busy[i] is not None:
             self._harvest(i)
-        self.slots[i].stage(t & _SEQ_MASK, clouds)     # a ValueError leaves the ticket unused and the slot free
+        if frustums is None:
+            self.slots[i].stage(t & _SEQ_MASK, clouds)     # a ValueError leaves the ticket unused and the slot free
+        else:
+            self.slots[i].stage(t & _SEQ_MASK, clouds, frustums)
         self.slots[i].launch()
         self.busy[i] = t
         self.next_ticket = t + 1
@@ -161,7 +239,8 @@ class FrameRing:
                 self._harvest(i)
 
     def map(self, batches):
-        """(ticket, result) per batch of `batches`, in order, with at most len(slots) frames submitted and not yet yielded."""
+        """(ticket, result) per batch of `batches`, in order, with at most len(slots) frames submitted and not yet yielded.
+        A batch is a list of clouds, or the tuple (clouds, frustums) for a stream with raw_cap."""
         pending = deque()
         try:
             batches = iter(batches)
@@ -173,7 +252,10 @@ class FrameRing:
                     clouds = next(batches)
                 except StopIteration:
                     break
-                pending.append(self.submit(clouds))
+                if isinstance(clouds, tuple):           # (clouds, frustums): a raw stream's batch
+                    pending.append(self.submit(*clouds))
+                else:
+                    pending.append(self.submit(clouds))
             while pending:
                 t = pending.popleft()
                 yield t, self.collect(t)
@@ -196,34 +278,41 @@ class FrameRing:
 
 class _PlanSlot:
     """One frame in flight: an InferencePlan captured with the seal as its last node, its HIP stream, a pinned staging block
-    [seq, npts[B] | B x points_cap x ndim f32], a pinned record buffer and the event behind the record's copy."""
+    [seq, npts[B] | B x points_cap x ndim f32], a pinned record buffer and the event behind the record's copy.
+    With raw_cap the frame crops: the block is [planes[B,6,4] f64 | seq, nraw[B] | B x raw_cap x ndim f32], the clouds go
+    to plan.raw_in and the plan's first nodes cut them down to points_cap rows of plan.pts_in."""
 
-    def __init__(self, plan, points_cap, ndim):
+    def __init__(self, plan, points_cap, ndim, raw_cap=None):
         import torch
         self.torch, self.plan = torch, plan
         dev, B = plan.dev, plan.B
         self.stream = torch.cuda.Stream(device=dev)
         with torch.cuda.stream(self.stream):
-            plan.capture(points_cap, ndim=ndim, seal=True)
+            plan.capture(points_cap, ndim=ndim, seal=True, raw_cap=raw_cap)
         self.stream.synchronize()
         self.cap, self.ndim = int(points_cap), int(ndim)
+        self.raw_cap = None if raw_cap is None else int(raw_cap)
         nwords = 1 + B
-        self.pin_words = torch.zeros(nwords, dtype=torch.int32).pin_memory()
-        self.pin_pts = torch.zeros(B, self.cap, self.ndim, dtype=torch.float32).pin_memory()
+        if self.raw_cap is None:
+            self.pin_words = torch.zeros(nwords, dtype=torch.int32).pin_memory()
+            self.dev_words, self.dev_pts, rows = plan._stage_words, plan.pts_in, self.cap
+        else:                                   # one pinned block shaped like plan._stage_block: planes, then the words
+            self.pin_block = torch.zeros(plan._stage_block.numel(), dtype=torch.uint8).pin_memory()
+            nplane = B * 6 * 4 * 8
+            self.np_planes = self.pin_block[:nplane].view(torch.float64).view(B, 6, 4).numpy()
+            self.pin_words = self.pin_block[nplane:].view(torch.int32)
+            self.dev_words, self.dev_pts, rows = plan._stage_block, plan.raw_in, self.raw_cap
+        self.pin_pts = torch.zeros(B, rows, self.ndim, dtype=torch.float32).pin_memory()
         self.pin_rec = torch.zeros(plan.record.numel(), dtype=torch.uint8).pin_memory()
         self.np_words, self.np_pts, self.np_rec = self.pin_words.numpy(), self.pin_pts.numpy(), self.pin_rec.numpy()
         self.event = torch.cuda.Event()
         self.feed = torch.cuda.Event()          # orders device-tensor clouds (produced on the caller's stream) before their copy
 
-    def stage(self, seq, clouds):
+    def stage(self, seq, clouds, frustums=None):
         torch, plan = self.torch, self.plan
-        if len(clouds) != plan.B:
-            raise ValueError("a batch of %d clouds for a stream of batch_size %d" % (len(clouds), plan.B))
-        for b, pts in enumerate(clouds):        # never detect on a silently truncated cloud; nothing is queued before this check
-            if pts.ndim != 2 or pts.shape[1] != self.ndim:
-                raise ValueError("cloud %d has shape %s, expected [N, %d]" % (b, tuple(pts.shape), self.ndim))
-            if pts.shape[0] > self.cap:
-                raise ValueError("cloud %d has %d points, the stream was sized for %d (points_cap)" % (b, pts.shape[0], self.cap))
+        planes = check_frame_inputs(clouds, frustums, plan.B, self.ndim, self.cap, self.raw_cap)   # nothing is queued before this
+        if planes is not None:
+            self.np_planes[...] = planes
         on_dev = [torch.is_tensor(p) and p.is_cuda for p in clouds]
         if any(on_dev):
             self.feed.record(torch.cuda.current_stream(plan.dev))
@@ -236,13 +325,13 @@ class _PlanSlot:
                 if n == 0:
                     continue
                 if on_dev[b]:
-                    plan.pts_in[b][:n].copy_(pts, non_blocking=True)
+                    self.dev_pts[b][:n].copy_(pts, non_blocking=True)
                     pts.record_stream(self.stream)      # the caller may drop the cloud now: its memory is not handed out
                                                         # again before this copy has run
                 else:
                     self.np_pts[b, :n] = pts.numpy() if torch.is_tensor(pts) else pts
-                    plan.pts_in[b][:n].copy_(self.pin_pts[b, :n], non_blocking=True)
-            plan._stage_words.copy_(self.pin_words, non_blocking=True)
+                    self.dev_pts[b][:n].copy_(self.pin_pts[b, :n], non_blocking=True)
+            self.dev_words.copy_(self.pin_words if self.raw_cap is None else self.pin_block, non_blocking=True)
 
     def launch(self):
         torch = self.torch
@@ -284,12 +373,18 @@ class FrameStream:
     submit() returns; a device cloud is read by a copy that may still be pending then -- the caller may DROP it at once (it is
     recorded on the slot's stream, so the allocator keeps its memory until the copy has run) but must not WRITE into it before
     the ticket has been collected.  A cloud of more than points_cap points raises
-    ValueError at submit, before anything is queued.  A frame whose status word is not zero raises plan.results()'s
+    ValueError at submit, before anything is queued.  With `raw_cap` the stream takes raw sweeps of up to raw_cap points:
+    every submit needs `frustums`, one per cloud -- a [6,4] float64 plane array (geometry.frustum_planes) or
+    dict(calib=..., img_shape=...) (frustum_of) -- the frame crops each cloud to its frustum on the GPU, in order, and
+    detects on the kept points exactly as if they had been submitted to a stream without raw_cap; a frame that keeps more
+    than points_cap points raises FrameStatusError with SASSD_ST_POINT_OVERFLOW (16) from its collect().  A cloud above
+    raw_cap, missing / miscounted frustums, planes that are not [6,4] float64 or not finite, and frustums given to a stream
+    without raw_cap raise ValueError at submit, before anything is queued.  A frame whose status word is not zero raises plan.results()'s
     RuntimeError from ITS collect(); a record that is not the ticket's own raises RuntimeError("stale frame record").
     `plans` are the InferencePlans (for tools); plan_kwargs go to InferencePlan (precision, sparse_precision, ...)."""
 
     def __init__(self, state_dict, inflight=3, points_cap=None, batch_size=1, anchors=None, device=None, ndim=4,
-                 **plan_kwargs):
+                 raw_cap=None, **plan_kwargs):
         from .pipeline import InferencePlan
         inflight = int(inflight)
         if not 1 <= inflight <= MAX_INFLIGHT:
@@ -298,15 +393,18 @@ class FrameStream:
             raise ValueError("points_cap (the largest cloud the stream accepts) is required")
         if "overlap" in plan_kwargs:
             raise ValueError("FrameStream chooses `overlap` itself: one-branch plans in flight, the two-branch plan alone")
+        if raw_cap is not None and int(raw_cap) < 1:
+            raise ValueError("raw_cap (the largest raw sweep the stream accepts) must be >= 1")
         self.inflight, self.points_cap, self.batch_size = inflight, int(points_cap), int(batch_size)
+        self.raw_cap = None if raw_cap is None else int(raw_cap)
         self.plans = [InferencePlan(state_dict, batch_size=batch_size, anchors=anchors, device=device,
                                     overlap=inflight == 1, **plan_kwargs) for _ in range(inflight)]
         B, capD = self.plans[0].B, self.plans[0].capD
-        self._slots = [_PlanSlot(p, self.points_cap, ndim) for p in self.plans]
+        self._slots = [_PlanSlot(p, self.points_cap, ndim, self.raw_cap) for p in self.plans]
         self._ring = FrameRing(self._slots, lambda rec, seq: decode_record(rec, B, capD, seq))
 
-    def submit(self, clouds):
-        return self._ring.submit(clouds)
+    def submit(self, clouds, frustums=None):
+        return self._ring.submit(clouds, frustums)
 
     def collect(self, ticket):
         return self._ring.collect(ticket)
