@@ -54,7 +54,9 @@ const char *sassd_last_hip_error_string(void);
  *     round-3 default (1 or 5 by capacity) for every layer; any other value returns SASSD_EINVAL.
  *   Winograd (sassd_conv2d_wino4_fwd / _chain, sassd_conv1x1_gemm_fwd)   bits 0-7 = GEMM geometry: 0 split operands on the
  *     bf16 MFMA, 128 x 128 workgroups (default); 1 = the fp32 MFMA (v_mfma_f32_32x32x2_f32) at its picked width; 2..6 = fp32
- *     MFMA with 32 cfg tile columns; 11..14 = split with other workgroup shapes.  Bits 8+: bit0 stage only the first chunk,
+ *     MFMA with 32 cfg tile columns; 11..14 = split with other workgroup shapes (12 = the 128 x 128 workgroup by number); 15 /
+ *     16 = split, 256 channels x 192 / 256 columns per workgroup on 128-row wave tiles.  All split geometries give bit-identical
+ *     results.  Bits 8+: bit0 stage only the first chunk,
  *     bit1 no MFMA (fp32 geometries), bit2 no split arithmetic, bits 4 / 5 / 6 / 7 skip the input transform / GEMM / output
  *     transform / fused transform (per-kernel timing on live buffers, bench.py).  Chained calls must agree on the geometry.
  * The Python binding reads SASSD_SPCONV_DEBUG / SASSD_WINO4_CFG once as the DEFAULT cfg its wrappers pass. */
@@ -391,7 +393,8 @@ int sassd_conv2d_wino4_chain(const float *x, int src_products, const float *prev
  * (ssd_rotate_head.py:424-429) on conv6's products.  One call = the fused transform of the previous call's products (prev_* = that
  * layer's folded BatchNorm / ReLU; y_prev, optional: its NCHW activation map, stored from the LDS plane for its other readers --
  * BEVNet conv7, cmn.py:262), the 36 GEMMs on a 64-channel block, the output transform + scale / shift / relu into y [B,Cout,H,W].
- * Weights: sassd_conv2d_wino4_pack_weight_narrow ([36][Cin][64], zero padded).  Default GEMM geometry only. */
+ * Weights: sassd_conv2d_wino4_pack_weight_narrow ([36][Cin][64], zero padded).  cfg: the geometry of the chain's other calls; this
+ * layer runs 128-column blocks on their planes, and a geometry whose plane stride is no multiple of 128 is SASSD_EINVAL. */
 size_t sassd_conv2d_wino4_narrow_packed_floats(int Cin);
 int sassd_conv2d_wino4_pack_weight_narrow(const float *w /*[Cout,Cin,3,3]*/, int Cout, int Cin, float *packed, void *stream);
 int sassd_conv2d_wino4_chain_tail(const float *prev_scale, const float *prev_shift, int prev_relu, float *y_prev,

@@ -20,8 +20,10 @@
 // GEMM kernel, round 4: the fp32 products run on the bf16 MFMA (16 x the fp32 MFMA's rate) over operands split exactly into
 // three bf16 pieces in registers -- half the MFMA cycles per fp32 product, the error of the fp32 instruction (2.1e-5 against
 // fp64 on a KITTI layer for both), operands still fp32 in HBM and LDS: see "fp32 products on the bf16 MFMA" below.  Workgroup
-// = 128 output channels x 128 tiles, four waves of 64 x 64.  The fp32-MFMA form (geometry 1..6 of the cfg word,
-// the default of rounds 2-3): workgroup = 128 output channels x 32 WN tiles of one Winograd position, 2 x WN waves, each a 64 x 32
+// = 128 output channels x 128 tiles, four waves of 64 x 64, or -- where the launch is many rounds of those -- the wide tile, 256
+// channels x 192 tiles, four waves of 128 x 96: 7 split values feed 12 MFMAs instead of 4 feeding 4, so the split's vector
+// instructions hide behind the MFMAs (the layer alone 147 -> 130 us at 2200 tiles; w4_wide_pays).  The fp32-MFMA form
+// (geometry 1..6 of the cfg word, the default of rounds 2-3): workgroup = 128 output channels x 32 WN tiles of one Winograd position, 2 x WN waves, each a 64 x 32
 // block = two v_mfma_f32_32x32x2_f32 accumulators sharing one B fragment.  A ([k][128 co]) and B ([k][32 WN t]) chunks
 // of 32 input channels are staged by global->LDS DMA in their natural row-major form (both operands are K-major with
 // the M / N index contiguous, so fragment reads are 32 consecutive dwords: conflict free), double buffered, one
@@ -417,25 +419,33 @@ __device__ __forceinline__ bf16x8 split_b(const float w)
     return __builtin_bit_cast(bf16x8, d);
 }
 
-// scheduling groups of one pipelined step: MFMA m, then the split arithmetic (8 VALU instructions per value) of its share
-// of the next step's NV fragment values
+// scheduling groups of one pipelined step: MFMA m, then its share of the split arithmetic of the next step's NV fragment
+// values.  The arithmetic is 8 VALU instructions per value; it is dealt out by INSTRUCTION, not by value, so that a wave tile
+// with fewer values than MFMAs (MT = 4: 7 or 8 values behind 12 or 16 MFMAs) puts 4-5 instructions behind every MFMA instead
+// of 8 behind some and none behind others -- an MFMA hides about five.  (MT = NB = 2: 8 behind each, as before.)
 template <int M, int NM, int NV>
 __device__ __forceinline__ void split_sched()
 {
     if constexpr (M < NM) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        constexpr int n = (M + 1) * NV / NM - M * NV / NM;
-        if constexpr (n > 0) __builtin_amdgcn_sched_group_barrier(0x002, 8 * n, 0);
+        constexpr int n = (M + 1) * 8 * NV / NM - M * 8 * NV / NM;
+        if constexpr (n > 0) __builtin_amdgcn_sched_group_barrier(0x002, n, 0);
         split_sched<M + 1, NM, NV>();
     }
 }
 
-// WM x WN waves; a wave owns a 64 x (32 NB) block = 2 x NB accumulators of v_mfma_f32_32x32x2_f32 (SPLIT = 0) or of
+// WM x WN waves; a wave owns a (32 MT) x (32 NB) block = MT x NB accumulators of v_mfma_f32_32x32x2_f32 (SPLIT = 0) or of
 // v_mfma_f32_32x32x16_bf16 over split operands (SPLIT = 1; 2: ablation without the split arithmetic).
-template <int WM, int WN, int NB, int KC, int SPLIT>
-__global__ void __launch_bounds__(WM * WN * 64) wino4_gemm_kernel(W4Gemm P)
+// MT = 4 (the wide tiles, 128 rows per wave): a step reads and splits 4 + NB values for 4 NB MFMAs -- 4.7 (NB = 3) or 4.0
+// (NB = 4) VALU instructions per MFMA instead of the 8 of the 64 x 64 tile.  NB = 3 keeps its 192 accumulators and the
+// fragments inside 256 registers (two workgroups per CU: the second launch bound); NB = 4 takes the whole accumulator file
+// (one workgroup per CU).  The MFMAs of one output element run in the same order for every tile shape: results are
+// bit-identical across the split geometries.
+constexpr int w4_min_waves(int MT, int NB) { return MT == 4 && NB == 3 ? 2 : 1; }
+constexpr bool w4_sliced(int MT, int KC) { return MT > 2 || KC < kKC; }      // epilogue in 32-row slices (below)
+template <int WM, int WN, int NB, int KC, int SPLIT, int MT = 2>
+__global__ void __launch_bounds__(WM * WN * 64, w4_min_waves(MT, NB)) wino4_gemm_kernel(W4Gemm P)
 {
-    constexpr int MT = 2;
     constexpr int NWV = WM * WN, WROWS = 32 * MT, BM = WROWS * WM, BN = 32 * NB * WN;
     constexpr int STAGE = (BM + BN) * KC;
     constexpr int NLA = KC * BM / 256, NLB = KC * BN / 256;          // 1 KB wave-loads per chunk
@@ -461,27 +471,56 @@ __global__ void __launch_bounds__(WM * WN * 64) wino4_gemm_kernel(W4Gemm P)
     const float *src[LPW];
     size_t kstride[LPW];
     int dst[LPW];
+    // (wide tiles) the same map with the address cut into a wave-uniform base (scalar registers; kstride is uniform too) and a
+    // 32-bit lane offset in bytes: wave-load t starts R qa + ra pieces into its operand (R = pieces per row), so lane l reads row
+    // qa + (ra + l) / R, piece (ra + l) % R.  The lane part depends on ra alone -- one register for all A loads (ra = 0) and one
+    // per distinct ra of the B loads (three at 192 columns, one at 256) instead of a 64-bit pointer per load: the 128 x 96 wave
+    // tile has no registers to spare.
+    constexpr bool UDMA = MT > 2;
+    const float *sbase[LPW];
+    unsigned voff[LPW];
 #pragma unroll
     for (int i = 0; i < LPW; ++i) {
         const int t = wave + NWV * i;
-        if (t < NLA) {
+        // (NLA a multiple of NWV: which operand load i stages is known at compile time, and so is which lane offsets coincide)
+        const bool is_a = (UDMA && NLA % NWV == 0) ? i < NLA / NWV : t < NLA;
+        if (is_a) {
             const int e = t * 64 + lane;
             src[i] = Ub + (size_t)(e / (BM / 4)) * P.Cout + (e % (BM / 4)) * 4;
             kstride[i] = (size_t)KC * P.Cout;
             dst[i] = t * 256;
+            constexpr int R = BM / 4;
+            const int qa = t * 64 / R, ra = t * 64 % R;
+            sbase[i] = Ub + (size_t)qa * P.Cout;
+            voff[i] = ((unsigned)((ra + lane) / R) * (unsigned)P.Cout + (unsigned)((ra + lane) % R) * 4u) * 4u;      // bytes
         } else {
             const int e = (t - NLA) * 64 + lane;
             src[i] = Vb + (size_t)(e / (BN / 4)) * P.ldv + (e % (BN / 4)) * 4;
             kstride[i] = (size_t)KC * P.ldv;
             dst[i] = BM * KC + (t - NLA) * 256;
+            constexpr int R = BN / 4;
+            const int qa = (t - NLA) * 64 / R, ra = (t - NLA) * 64 % R;
+            sbase[i] = Vb + (size_t)qa * P.ldv;
+            voff[i] = ((unsigned)((ra + lane) / R) * (unsigned)P.ldv + (unsigned)((ra + lane) % R) * 4u) * 4u;
         }
     }
     auto dma = [&](int chunk, float *stage) {
 #pragma unroll
         for (int i = 0; i < LPW; ++i)
-            if (wave + NWV * i < NLA + NLB)
-                __builtin_amdgcn_global_load_lds((glb_ptr_t)(src[i] + chunk * kstride[i]), (lds_ptr_t)(stage + dst[i]), 16,
-                                                 0, 0);
+            if ((NLA + NLB) % NWV == 0 || wave + NWV * i < NLA + NLB) {
+                if constexpr (UDMA) {
+                    // (the empty asm statements pin the chunk's base in scalar registers and the lane offset in ONE register: left
+                    // to itself the compiler keeps a 64-bit lane pointer per load alive across the chunk loop and advances each
+                    // by kstride.  Base + zero-extended offset, formed here, selects the scalar-base addressing mode.)
+                    unsigned long long ub = (unsigned long long)(sbase[i] + chunk * kstride[i]);
+                    unsigned vo = voff[i];
+                    asm volatile("" : "+s"(ub));
+                    asm volatile("" : "+v"(vo));
+                    __builtin_amdgcn_global_load_lds((glb_ptr_t)((const char *)ub + vo), (lds_ptr_t)(stage + dst[i]), 16, 0, 0);
+                } else
+                    __builtin_amdgcn_global_load_lds((glb_ptr_t)(src[i] + chunk * kstride[i]), (lds_ptr_t)(stage + dst[i]), 16,
+                                                     0, 0);
+            }
     };
     const int wm = wave % WM, wn = wave / WM;
     const int l31 = lane & 31, kh = lane >> 5;
@@ -534,7 +573,8 @@ __global__ void __launch_bounds__(WM * WN * 64) wino4_gemm_kernel(W4Gemm P)
                             acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[cur][a], fr[cur][MT + b], acc[a][b], 0, 0, 0);
                             if (more) {
 #pragma unroll
-                                for (int v = m * NV / NM; v < (m + 1) * NV / NM; ++v) fr[nxt][v] = mk(v);
+                                for (int v = 0; v < NV; ++v)
+                                    if (v * NM / NV == m) fr[nxt][v] = mk(v);
                             }
                         }
                     if (more) split_sched<0, NM, NV>();
@@ -579,6 +619,38 @@ __global__ void __launch_bounds__(WM * WN * 64) wino4_gemm_kernel(W4Gemm P)
     // Epilogue through LDS (the staging buffers are dead): D[row = (r & 3) + 8 * (r >> 2) + 4 * kh][col = l31] goes to the
     // wave's [32 MT][32 NB] image, then 16-byte row stores (a dword store per accumulator register is ~6x slower per byte)
     constexpr int WCOLS = 32 * NB;
+    const bool epi = P.scale || P.shift || P.relu;
+    if constexpr (w4_sliced(MT, KC)) {
+        // ... in 32-row slices, one accumulator row `a` at a time: the image of a whole 128-row wave tile (48-64 KB per wave)
+        // would decide the workgroup's LDS, and so would the 64-row image beside 16-channel staging buffers.  The slice is
+        // wave-private and LDS serves one wave's accesses in order: slice a + 1 is written behind the reads of slice a.
+        float *img = lds + wave * 32 * WCOLS;
+        constexpr int C4 = WCOLS / 4;                   // float4 per row
+        static_assert(32 * C4 % 64 == 0, "whole wave-instructions per slice");
+#pragma unroll
+        for (int a = 0; a < MT; ++a) {
+#pragma unroll
+            for (int b = 0; b < NB; ++b)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) img[((r & 3) + 8 * (r >> 2) + 4 * kh) * WCOLS + b * 32 + l31] = acc[a][b][r];
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            const int co0 = mb * BM + wm * WROWS + a * 32;
+            float *Mb = P.M + (size_t)p * P.sm + (size_t)co0 * P.ldm + nb * BN + wn * WCOLS;
+#pragma unroll
+            for (int i = 0; i < 32 * C4 / 64; ++i) {
+                const int e = i * 64 + lane, row = e / C4, c4 = e % C4;
+                float4 v = *reinterpret_cast<const float4 *>(img + row * WCOLS + c4 * 4);
+                if (epi) {
+                    const float sc = P.scale ? P.scale[co0 + row] : 1.f, sh = P.shift ? P.shift[co0 + row] : 0.f;
+                    v.x = v.x * sc + sh; v.y = v.y * sc + sh; v.z = v.z * sc + sh; v.w = v.w * sc + sh;
+                    if (P.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+                }
+                *reinterpret_cast<float4 *>(Mb + (size_t)row * P.ldm + c4 * 4) = v;
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the slice has been read before it is written again
+        }
+        return;
+    }
     float *img = lds + wave * WROWS * WCOLS;
 #pragma unroll
     for (int a = 0; a < MT; ++a)
@@ -591,7 +663,6 @@ __global__ void __launch_bounds__(WM * WN * 64) wino4_gemm_kernel(W4Gemm P)
     const int co0 = mb * BM + wm * WROWS;
     float *Mb = P.M + (size_t)p * P.sm + (size_t)co0 * P.ldm + nb * BN + wn * WCOLS;
     constexpr int C4 = WCOLS / 4, RPI = 64 / C4;        // float4 per row, rows per wave-instruction
-    const bool epi = P.scale || P.shift || P.relu;
 #pragma unroll
     for (int i = 0; i < WROWS / RPI; ++i) {
         const int row = i * RPI + lane / C4, c4 = lane % C4;
@@ -611,18 +682,21 @@ __global__ void __launch_bounds__(WM * WN * 64) wino4_gemm_kernel(W4Gemm P)
 inline int w4_geo(int cfg) { return cfg & 0xff; }
 inline int w4_dbg(int cfg) { return cfg >> 8; }
 
-template <int WM, int WN, int NB, int KC, int SPLIT = 0>
+template <int WM, int WN, int NB, int KC, int SPLIT = 0, int MT = 2>
 int launch_w4_gemm(W4Gemm P, int dbg, hipStream_t stream)
 {
-    constexpr int BM = 64 * WM, BN = 32 * NB * WN;
-    static_assert(BM == kBM || (WM == 1 && SPLIT != 0), "the channel block is fixed (w4_pick_wn and the supported() checks price "
-                                                        "it); the one exception is the 64-channel block of a narrow tail layer");
-    constexpr size_t stage_b = (size_t)2 * (BM + BN) * KC * 4, img_b = (size_t)WM * WN * 64 * 32 * NB * 4;
-    constexpr size_t lds = stage_b > img_b ? stage_b : img_b;        // the epilogue image reuses the staging buffers
+    constexpr int BM = 32 * MT * WM, BN = 32 * NB * WN;
+    static_assert(BM == kBM || (WM == 1 && SPLIT != 0) || (BM == 2 * kBM && SPLIT != 0),
+                  "the channel block is fixed (w4_pick_wn and the supported() checks price it); the exceptions are the 64-channel "
+                  "block of a narrow tail layer and the 256-channel block of the wide split tiles (supported(): Cout % 256 == 0)");
+    // the epilogue image reuses the staging buffers: the whole wave tile, or one 32-row slice of it per wave
+    constexpr size_t stage_b = (size_t)2 * (BM + BN) * KC * 4;
+    constexpr size_t img_b = (size_t)WM * WN * (w4_sliced(MT, KC) ? 32 : 32 * MT) * 32 * NB * 4;
+    constexpr size_t lds = stage_b > img_b ? stage_b : img_b;
     if constexpr (SPLIT == 1)
-        if (dbg & 4) return launch_w4_gemm<WM, WN, NB, KC, 2>(P, dbg, stream);      // ablation instance
+        if (dbg & 4) return launch_w4_gemm<WM, WN, NB, KC, 2, MT>(P, dbg, stream);      // ablation instance
     static std::atomic<unsigned long long> attr_done{0};
-    const void *fn = (const void *)wino4_gemm_kernel<WM, WN, NB, KC, SPLIT>;
+    const void *fn = (const void *)wino4_gemm_kernel<WM, WN, NB, KC, SPLIT, MT>;
     int rc = sassd_dyn_lds(fn, lds, attr_done);
     if (rc) return rc;
     P.nmb = P.Cout / BM; P.nnb = P.ncols / BN;
@@ -633,7 +707,7 @@ int launch_w4_gemm(W4Gemm P, int dbg, hipStream_t stream)
     P.seglen = cdiv(P.nnb, P.nseg);
     P.pairs_per_xcd = cdiv(pairs * P.nseg, 8);
     P.dbg = dbg;
-    hipLaunchKernelGGL((wino4_gemm_kernel<WM, WN, NB, KC, SPLIT>), dim3(8 * P.pairs_per_xcd * P.seglen), dim3(WM * WN * 64),
+    hipLaunchKernelGGL((wino4_gemm_kernel<WM, WN, NB, KC, SPLIT, MT>), dim3(8 * P.pairs_per_xcd * P.seglen), dim3(WM * WN * 64),
                        lds, stream, P);
     return sassd_launch_status();
 }
@@ -662,33 +736,60 @@ inline int w4_pick_wn(int T, int Cout, int np = 36, bool exact = false)
 
 // Geometry of the Winograd GEMM launch.  Default: fp32 products on the bf16 MFMA over split operands, 128 channels x 128
 // tiles per workgroup, four waves of 64 x 64 (measured at 2200 tiles: 142 us per 256 -> 256 layer with its two transform
-// launches against 157 for the best fp32-MFMA geometry; 64 columns 160, 192 columns 170).  geometry (cfg bits 0-7): 0 = default, 1 = the
+// launches against 157 for the best fp32-MFMA geometry; 64 columns 160, 192 columns 170) or the wide tile below.  geometry (cfg
+// bits 0-7): 0 = default, 1 = the
 // fp32 MFMA at its picked width (the round-3 default), 2..6 = the fp32 MFMA with 32 cfg columns, 11..13 = split with
-// 64 (cfg - 10) columns, 14 = split, 128 columns, 16-channel chunks.
+// 64 (cfg - 10) columns (12 = the 128 x 128 workgroup by number, whatever the default picks), 14 = split, 128 columns, 16-channel
+// chunks.
+// The default (0) picks between the 128 x 128 workgroup and the wide 256 x 192 one by the rounds model of w4_pick_wn: both shapes
+// keep two workgroups on a CU (512 slots), a launch takes ceil(workgroups / 512) rounds, and a round of wide workgroups was
+// measured at about twice a round of 128 x 128 ones for three times the MFMAs (KITTI, 2200 tiles: 3 rounds against 1, the layer
+// 147 -> 130 us; profiles/wino4_wide_tiles_kernel.txt).  Wide when it is cheaper by that count; a small map that fills no round stays
+// on the small workgroup, which finishes sooner.
+inline bool w4_wide_pays(int T, int Cout)
+{
+    const long small = 36L * (Cout / kBM) * cdiv(T, 128), wide = 36L * (Cout / (2 * kBM)) * cdiv(T, 192);
+    return 2 * ((wide + 511) / 512) < (small + 511) / 512;
+}
+
+// 15 / 16 = the wide split tiles: 256 channels x 192 / 256 columns per workgroup, four waves of 128 x 96 / 128 x 128, 16-channel
+// chunks (56 / 64 KB of staging: two workgroups / one per CU).
 struct W4Tile {
-    int split, wn, nb, kc;
+    int split, wn, nb, kc, mt;
     int bn() const { return 32 * nb * wn; }
+    // plane stride of V and M in units of this: 192-column blocks pad the planes to a multiple of 384, so that the 128-column
+    // kernels that share a chain's planes (the narrow tail layer) find whole blocks of their own in them
+    int stride_unit() const { return bn() % 128 ? 2 * bn() : bn(); }
 };
 inline W4Tile w4_tile(int T, int Cout, int geo)
 {
     const int c = geo;
-    if (c >= 2 && c <= 6) return W4Tile{0, c, 1, kKC};
-    if (c >= 11 && c <= 13) return W4Tile{1, c - 10, 2, kKC};
-    if (c == 14) return W4Tile{1, 2, 2, 16};
-    if (c == 1) return W4Tile{0, w4_pick_wn(T, Cout), 1, kKC};
-    return W4Tile{1, 2, 2, kKC};
+    if (c >= 2 && c <= 6) return W4Tile{0, c, 1, kKC, 2};
+    if (c >= 11 && c <= 13) return W4Tile{1, c - 10, 2, kKC, 2};
+    if (c == 14) return W4Tile{1, 2, 2, 16, 2};
+    if (c == 15) return W4Tile{1, 2, 3, 16, 4};
+    if (c == 16) return W4Tile{1, 2, 4, 16, 4};
+    if (c == 1) return W4Tile{0, w4_pick_wn(T, Cout), 1, kKC, 2};
+    if (c == 0 && w4_wide_pays(T, Cout)) return W4Tile{1, 2, 3, 16, 4};
+    return W4Tile{1, 2, 2, kKC, 2};
 }
 
+// plane stride Tp of V [36][Cin][Tp] and M [36][Cout][Tp]: one value for every layer of a chain (same T, same cfg)
 inline int w4_tiles_padded(int B, int H, int W, int Cout, int geo)
 {
     const int T = B * (H / 4) * (W / 4);
-    const int bn = w4_tile(T, Cout, geo).bn();
-    return cdiv(T, bn) * bn;
+    const W4Tile t = w4_tile(T, Cout, geo);
+    const int u = t.mt == 4 ? t.stride_unit() : t.bn();
+    return cdiv(T, u) * u;
 }
+// columns one GEMM launch covers: whole column blocks of ITS width over the T tiles (<= the plane stride)
+inline int w4_gemm_cols(int T, int bn) { return cdiv(T, bn) * bn; }
 
 inline int w4_launch(const W4Tile t, const W4Gemm &P, int dbg, hipStream_t stream)
 {
     if (t.split) {
+        if (t.mt == 4) return t.nb == 3 ? launch_w4_gemm<2, 2, 3, 16, 1, 4>(P, dbg, stream)
+                                        : launch_w4_gemm<2, 2, 4, 16, 1, 4>(P, dbg, stream);
         if (t.kc == 16) return launch_w4_gemm<2, 2, 2, 16, 1>(P, dbg, stream);
         switch (t.wn) {
         case 1: return launch_w4_gemm<2, 1, 2, kKC, 1>(P, dbg, stream);
@@ -759,7 +860,8 @@ extern "C" int sassd_conv2d_wino4_fwd(const float *x, const float *w_packed, con
         hipLaunchKernelGGL(wino4_in_kernel, dim3(cdiv(G.T, 256), Cin), dim3(256), 0, stream, x, G, V, (const int32_t *)nullptr);
     W4Gemm P;
     P.U = w_packed; P.V = V; P.M = M; P.scale = nullptr; P.shift = nullptr; P.relu = 0; P.ncols_dev = nullptr;
-    P.np = 36; P.Cin = Cin; P.Cout = Cout; P.ldv = G.Tp; P.ldm = G.Tp; P.ncols = G.Tp;
+    P.np = 36; P.Cin = Cin; P.Cout = Cout; P.ldv = G.Tp; P.ldm = G.Tp;
+    P.ncols = w4_gemm_cols(G.T, w4_tile(G.T, Cout, geo).bn());
     P.su = (size_t)Cin * Cout; P.sv = (size_t)Cin * G.Tp; P.sm = (size_t)Cout * G.Tp;
     int rc = SASSD_OK;
     if (!(dbg & 32)) rc = w4_launch(w4_tile(G.T, Cout, geo), P, dbg, stream);
@@ -831,7 +933,8 @@ extern "C" int sassd_conv2d_wino4_chain(const float *x, int src_products, const 
     }
     W4Gemm P;
     P.U = w_packed; P.V = V; P.M = M; P.scale = nullptr; P.shift = nullptr; P.relu = 0; P.ncols_dev = tile_map;
-    P.np = 36; P.Cin = Cin; P.Cout = Cout; P.ldv = G.Tp; P.ldm = G.Tp; P.ncols = G.Tp;
+    P.np = 36; P.Cin = Cin; P.Cout = Cout; P.ldv = G.Tp; P.ldm = G.Tp;
+    P.ncols = w4_gemm_cols(G.T, w4_tile(G.T, Cout, geo).bn());
     P.su = (size_t)Cin * Cout; P.sv = (size_t)Cin * G.Tp; P.sm = (size_t)Cout * G.Tp;
     int rc = SASSD_OK;
     if (!(dbg & 32)) rc = w4_launch(w4_tile(G.T, Cout, geo), P, dbg, stream);
@@ -870,7 +973,9 @@ extern "C" int sassd_conv2d_wino4_chain_tail(const float *prev_scale, const floa
 {
     const int geo = w4_geo(cfg), dbg = w4_dbg(cfg);
     if (!w_packed64 || !y || !workspace || batch < 1 || Cout < 1 || Cout > 64 || cmax < Cin || cmax < 64) return SASSD_EINVAL;
-    if (!sassd_conv2d_wino4_chain_supported(Cin, 256, H, W) || geo != 0) return SASSD_EINVAL;     // (default geometry only)
+    if (!sassd_conv2d_wino4_chain_supported(Cin, 256, H, W)) return SASSD_EINVAL;
+    // this layer's GEMM runs 128-column blocks on the chain's planes: the chain's geometry must leave whole ones
+    if (w4_tiles_padded(batch, H, W, 256, geo) % 128) return SASSD_EINVAL;
     if (((uintptr_t)y & 15) || (y_prev && ((uintptr_t)y_prev & 15)) || ((uintptr_t)w_packed64 & 15) || ((uintptr_t)workspace & 15))
         return SASSD_EINVAL;
     const size_t need = sassd_conv2d_wino4_chain_workspace_bytes(batch, cmax, H, W);
@@ -878,7 +983,7 @@ extern "C" int sassd_conv2d_wino4_chain_tail(const float *prev_scale, const floa
     hipStream_t stream = (hipStream_t)stream_;
     W4Geom G;
     G.B = batch; G.C = Cin; G.H = H; G.W = W; G.TH = H / 4; G.TW = W / 4; G.T = batch * G.TH * G.TW;
-    G.Tp = w4_tiles_padded(batch, H, W, 256, geo);            // the previous (256-channel) layer's plane stride: same 128-column block
+    G.Tp = w4_tiles_padded(batch, H, W, 256, geo);            // the previous (256-channel) layer's plane stride
     float *V = (float *)workspace;
     float *M = (float *)((char *)workspace + need / 2);
     int rc;
@@ -887,7 +992,7 @@ extern "C" int sassd_conv2d_wino4_chain_tail(const float *prev_scale, const floa
         return rc;
     W4Gemm P;
     P.U = w_packed64; P.V = V; P.M = M; P.scale = nullptr; P.shift = nullptr; P.relu = 0; P.ncols_dev = nullptr;
-    P.np = 36; P.Cin = Cin; P.Cout = 64; P.ldv = G.Tp; P.ldm = G.Tp; P.ncols = G.Tp;
+    P.np = 36; P.Cin = Cin; P.Cout = 64; P.ldv = G.Tp; P.ldm = G.Tp; P.ncols = w4_gemm_cols(G.T, 128);
     P.su = (size_t)Cin * 64; P.sv = (size_t)Cin * G.Tp; P.sm = (size_t)64 * G.Tp;
     if (!(dbg & 32) && (rc = launch_w4_gemm<1, 2, 2, kKC, 1>(P, dbg, stream))) return rc;
     W4Geom Go = G;
@@ -1132,7 +1237,8 @@ extern "C" int sassd_conv2d_wino4_chain_sparse(const float *feats, int C, int D,
                            tile_map);
     W4Gemm P;
     P.U = w_packed; P.V = V; P.M = M; P.scale = nullptr; P.shift = nullptr; P.relu = 0; P.ncols_dev = tile_map;
-    P.np = 36; P.Cin = Cin; P.Cout = Cout; P.ldv = G.Tp; P.ldm = G.Tp; P.ncols = G.Tp;
+    P.np = 36; P.Cin = Cin; P.Cout = Cout; P.ldv = G.Tp; P.ldm = G.Tp;
+    P.ncols = w4_gemm_cols(G.T, w4_tile(G.T, Cout, geo).bn());
     P.su = (size_t)Cin * Cout; P.sv = (size_t)Cin * G.Tp; P.sm = (size_t)Cout * G.Tp;
     int rc = SASSD_OK;
     if (!(dbg & 32)) rc = w4_launch(w4_tile(G.T, Cout, geo), P, dbg, stream);

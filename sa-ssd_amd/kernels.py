@@ -284,7 +284,8 @@ def spconv_cfg(geometry=0, flags=0):
 
 
 def wino4_cfg(geometry=0, dbg=0):
-    """cfg word of the Winograd entry points: GEMM geometry (bits 0-7) + ablation / stage-skip flags."""
+    """cfg word of the Winograd entry points: GEMM geometry (bits 0-7: 0 = picked per shape, 12 = 128 x 128 workgroup, 15 / 16 = the
+    wide 256 x 192 / 256 x 256 ones, include/sassd.h) + ablation / stage-skip flags."""
     return (int(geometry) & 0xFF) | (int(dbg) << 8)
 
 

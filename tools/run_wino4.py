@@ -57,9 +57,10 @@ with torch.no_grad():
     ref64 = (ref64 * sc.double()[None, :, None, None] + sh.double()[None, :, None, None]).clamp(min=0)
     del cols
 print("F(2x2) fused vs fp64: max abs %.2e   (max |y| %.2f)" % ((ref.double() - ref64).abs().max().item(), ref64.abs().max().item()))
-names = {0: "split 128x128 (default)", 1: "fp32 auto", 2: "fp32 128x64", 3: "fp32 128x96", 4: "fp32 128x128", 5: "fp32 128x160",
-         6: "fp32 128x192", 11: "split 128x64", 12: "split 128x128", 13: "split 128x192", 14: "split 128x128 kc16"}
-cfgs = tuple(int(c) for c in args.cfgs.split(",")) if args.cfgs else (0, 1, 2, 3, 4, 5, 6, 11, 12, 13, 14)
+names = {0: "default (picked)", 1: "fp32 auto", 2: "fp32 128x64", 3: "fp32 128x96", 4: "fp32 128x128", 5: "fp32 128x160",
+         6: "fp32 128x192", 11: "split 128x64", 12: "split 128x128", 13: "split 128x192", 14: "split 128x128 kc16", 15: "split 256x192 wide",
+         16: "split 256x256 wide"}
+cfgs = tuple(int(c) for c in args.cfgs.split(",")) if args.cfgs else (0, 1, 2, 3, 4, 5, 6, 11, 12, 13, 14, 15, 16)
 for cfg in cfgs:
     line = "cfg %2d %-22s" % (cfg, names[cfg])
     split = cfg >= 11 or cfg == 0
