@@ -647,6 +647,57 @@ int sassd_frame_seal(const float *boxes, const float *scores, const int32_t *lab
                      size_t record_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * KITTI annotations: what kitti_common.kitti_bbox2results computes per frame on the host -- the camera-frame result
+ * annotation of every detection whose projection meets the image -- as one more kernel node of the captured frame.
+ * sassd_frame_annos READS boxes [B][capD][7] f32 (x, y, z, w, l, h, yaw; lidar frame), counts [B] and the calibration
+ * block, and writes nothing but `annos`.  One launch, one workgroup per sample, plain loads and vector stores: no
+ * atomics, no memset.
+ *
+ * Calibration block: per sample 36 float64 -- Tr_velo_to_cam [3][4], R0_rect [3][3], P2 [3][4], img_w, img_h, one pad.
+ *
+ * ARITHMETIC (csrc/kitti_anno_core.h states it once, for the kernel and for the CPU harness of the tests; products are
+ * rounded separately, every sum is associated left to right):
+ *   yaw'        = yaw - floor(yaw / 2pi + 0.5) * 2pi                      float32, 2pi rounded to float32
+ *   location    = R0 . (V2C . [x y z 1])                                  float64, rounded to float32
+ *   dimensions  = (l, h, w);  rotation_y = yaw'
+ *   corners     = ((+-0.5, {-1, 0}, +-0.5) * (l, h, w)) rotated about the camera y axis by yaw' (float32 sin / cos),
+ *                 plus the float32 location                               float32
+ *   (u, v, w)   = P2 . [X Y Z 1] per corner, u / w and v / w              float64
+ *   bbox        = min u, min v, max u, max v over the eight corners       float64
+ *   alpha       = -atan2(-y, x) + yaw'                                    float32
+ *   keep        = !(x1 > img_w || y1 > img_h || x2 < 0 || y2 < 0)
+ *   clip        = x1, y1 to >= 0;  x2 to <= img_w;  y2 to <= img_h
+ * A box with corners at or behind the image plane gets NO special case: the formula is applied as written, as the host
+ * function applies it (a negative w mirrors the corner, w == 0 gives an infinite coordinate).  The min / max are plain
+ * comparisons, so a NaN coordinate (non-finite input) is ignored where numpy would propagate it.
+ *
+ * CONTRACT -- the annotation block, in 32-bit words from its 8-byte aligned start, n = B * capD:
+ *   kept  [B] i32          annotation rows of sample b; one zero word follows when B is odd
+ *   index [B][capD] i32    the detection row each annotation row came from, ascending (stable compaction: score order)
+ *   cam   [B][capD][7] f32 x, y, z, l, h, w, rotation_y
+ *   alpha [B][capD] f32    one zero word follows when n is odd, so that
+ *   bbox  [B][capD][4] f64 is 8-byte aligned
+ * counts[b] is clamped to 0 .. capD as in the frame record; every row at or past kept[b] is written as zero words, so the
+ * block is a pure function of the frame.  sassd_frame_annos_bytes is its size, 0 for an impossible shape.  `calib` and
+ * `annos` must be 8-byte aligned, boxes / counts 4-byte aligned (SASSD_EINVAL); annos_bytes at least the size
+ * (SASSD_ENOSPC).
+ *
+ * Frame record, layout version 2 (additive; version 1 is unchanged): SASSD_FRAME_MAGIC_KITTI in word 0, the version 1
+ * header and body as above, zero bytes up to the next 8-byte boundary, then the annotation block -- one buffer, one
+ * copy to the host.  sassd_frame_seal_kitti writes it (two kernel launches: the seal, then sassd_frame_annos on the same
+ * boxes / counts); `record` must be 8-byte aligned and record_bytes at least sassd_frame_record_kitti_bytes
+ * (= sassd_frame_record_bytes rounded up to 8, plus sassd_frame_annos_bytes).
+ * ---------------------------------------------------------------------------------------------- */
+#define SASSD_FRAME_MAGIC_KITTI 0x53460002                 /* 'S' 'F', layout version 2 */
+size_t sassd_frame_annos_bytes(int batch, int capD);
+int sassd_frame_annos(const float *boxes, const int32_t *counts, int batch, int capD, const double *calib,
+                      void *annos, size_t annos_bytes, void *stream);
+size_t sassd_frame_record_kitti_bytes(int batch, int capD);
+int sassd_frame_seal_kitti(const float *boxes, const float *scores, const int32_t *labels, const int32_t *counts,
+                           int batch, int capD, const int32_t *seq, const int32_t *status, const double *calib,
+                           void *record, size_t record_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * iou3d_cuda operator surface (mmdet/ops/iou3d/src/iou3d.cpp:31,52,73; kernels iou3d_kernel.cu:223-292).
  * boxes (x1,y1,x2,y2,ry) f32.  nms: boxes sorted by descending score; keep [n] i64 and num_keep are DEVICE
  * buffers (the reference fills a CPU LongTensor after a blocking D2H of the mask, iou3d.cpp:92-94).

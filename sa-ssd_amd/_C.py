@@ -98,6 +98,11 @@ _SIGS = {
     # frame record (include/sassd.h "Frame record"; sassd.stream)
     "sassd_frame_record_bytes": (_SZ, [_I, _I]),
     "sassd_frame_seal": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _SZ, _P]),
+    # KITTI annotations inside the frame, frame record layout version 2 (include/sassd.h "KITTI annotations")
+    "sassd_frame_annos_bytes": (_SZ, [_I, _I]),
+    "sassd_frame_annos": (_I, [_P, _P, _I, _I, _P, _P, _SZ, _P]),
+    "sassd_frame_record_kitti_bytes": (_SZ, [_I, _I]),
+    "sassd_frame_seal_kitti": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "sassd_boxes_overlap_bev": (_I, [_P, _I, _P, _I, _P, _P]),
     "sassd_boxes_iou_bev": (_I, [_P, _I, _P, _I, _P, _P]),
     "sassd_nms_workspace_bytes": (_SZ, [_I]),

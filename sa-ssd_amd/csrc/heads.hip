@@ -757,6 +757,7 @@ struct SealParams {
     const int32_t *seq; const int32_t *status;
     int32_t *rec;
     int B, capD, hdr;
+    int magic, pad;             // the layout version written to word 0; zero words written behind the body (layout 2: 0 or 1)
 };
 
 __device__ __forceinline__ int seal_count(const SealParams &P, int b)
@@ -771,7 +772,7 @@ __global__ void __launch_bounds__(256) frame_seal_kernel(SealParams P)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < P.hdr) {
         int v = 0;
-        if (i == 0) v = SASSD_FRAME_MAGIC;
+        if (i == 0) v = P.magic;
         else if (i == 1) v = P.seq[0];
         else if (i == 2) v = P.status[0];
         else if (i == 3) v = P.B;
@@ -783,6 +784,7 @@ __global__ void __launch_bounds__(256) frame_seal_kernel(SealParams P)
     float *rb = (float *)(P.rec + P.hdr);
     float *rs = rb + (size_t)7 * N;
     int32_t *rl = (int32_t *)(rs + N);
+    if (i < P.pad) rl[N + i] = 0;
 #pragma unroll
     for (int k = 0; k < 7; ++k) {
         const int e = i + k * N, row = e / 7, b = row / P.capD;
@@ -811,9 +813,38 @@ extern "C" int sassd_frame_seal(const float *boxes, const float *scores, const i
     SealParams P;
     P.boxes = boxes; P.scores = scores; P.labels = labels; P.counts = counts; P.seq = seq; P.status = status;
     P.rec = (int32_t *)record; P.B = batch; P.capD = capD; P.hdr = SASSD_FRAME_HEADER_WORDS(batch);
+    P.magic = SASSD_FRAME_MAGIC; P.pad = 0;
     const int threads = batch * capD > P.hdr ? batch * capD : P.hdr;
     hipLaunchKernelGGL(frame_seal_kernel, dim3(cdiv(threads, 256)), dim3(256), 0, (hipStream_t)stream_, P);
     return sassd_launch_status();
+}
+
+// Layout version 2: the version 1 header and body under SASSD_FRAME_MAGIC_KITTI, then the annotation block of
+// sassd_frame_annos (kitti_anno.hip) at the next 8-byte boundary.  Two launches, both plain kernels.
+extern "C" size_t sassd_frame_record_kitti_bytes(int batch, int capD)
+{
+    const size_t v1 = sassd_frame_record_bytes(batch, capD), an = sassd_frame_annos_bytes(batch, capD);
+    return v1 && an ? align_up(v1, 8) + an : 0;
+}
+
+extern "C" int sassd_frame_seal_kitti(const float *boxes, const float *scores, const int32_t *labels, const int32_t *counts,
+                                      int batch, int capD, const int32_t *seq, const int32_t *status, const double *calib,
+                                      void *record, size_t record_bytes, void *stream_)
+{
+    if (!boxes || !scores || !labels || !counts || !seq || !status || !calib || !record) return SASSD_EINVAL;
+    const size_t need = sassd_frame_record_kitti_bytes(batch, capD);
+    if (need == 0 || ((uintptr_t)record & 7) || ((uintptr_t)calib & 7)) return SASSD_EINVAL;
+    if (record_bytes < need) return SASSD_ENOSPC;
+    const size_t v1 = sassd_frame_record_bytes(batch, capD), at = align_up(v1, 8);
+    SealParams P;
+    P.boxes = boxes; P.scores = scores; P.labels = labels; P.counts = counts; P.seq = seq; P.status = status;
+    P.rec = (int32_t *)record; P.B = batch; P.capD = capD; P.hdr = SASSD_FRAME_HEADER_WORDS(batch);
+    P.magic = SASSD_FRAME_MAGIC_KITTI; P.pad = (int)((at - v1) / 4);
+    const int threads = batch * capD > P.hdr ? batch * capD : P.hdr;
+    hipLaunchKernelGGL(frame_seal_kernel, dim3(cdiv(threads, 256)), dim3(256), 0, (hipStream_t)stream_, P);
+    const int rc = sassd_launch_status();
+    if (rc != SASSD_OK) return rc;
+    return sassd_frame_annos(boxes, counts, batch, capD, calib, (char *)record + at, record_bytes - at, stream_);
 }
 
 extern "C" int sassd_boxes_overlap_bev(const float *boxes_a, int num_a, const float *boxes_b, int num_b,

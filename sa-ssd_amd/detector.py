@@ -27,7 +27,7 @@ from . import train_ops as T
 from . import weight_images
 from .autograd import bf16_cout_pad, bn_relu_conv, bn_relu_conv_fusable, AuxHeadFn, Conv2dFn, FocalLossFn, GuidedDecodeFn, PSWarpBatchFn, PSWarpFn, RpnLossFn, bev_precision, bn_relu_2d
 from .config import _wrap, obj_from_dict
-from .kitti_common import kitti_bbox2results
+from .kitti_common import kitti_bbox2results, result_anno_from_cam
 from .pipeline import InferencePlan
 from .pointnet2_utils import nearest_neighbor_interpolate
 
@@ -983,10 +983,14 @@ class SingleStageDetector(nn.Module):
 
     def result_annos(self, results, img_meta):
         """Per-sample detections (boxes, scores, labels) as InferencePlan.results() / FrameStream.collect() return them ->
-        what forward_test returns for these img_meta (its docstring)."""
+        what forward_test returns for these img_meta (its docstring).  A sample of a FrameStream(annos=True) frame is
+        (boxes, scores, labels, cam): its annotation was computed inside the frame and is only assembled here."""
         out = []
-        for (boxes, scores, labels), meta in zip(results, img_meta):
-            if isinstance(meta, dict) and meta.get('calib') is not None:
+        for res, meta in zip(results, img_meta):
+            boxes, scores, labels = res[:3]
+            if len(res) == 4 and isinstance(meta, dict) and meta.get('calib') is not None:
+                out.append(result_anno_from_cam(res[3], scores, labels, meta['sample_idx'], self.class_names))
+            elif isinstance(meta, dict) and meta.get('calib') is not None:
                 out.append(kitti_bbox2results(boxes, scores, labels, meta, class_names=self.class_names))
             else:
                 out.append(dict(boxes_lidar=boxes, scores=scores, labels=labels))

@@ -1035,6 +1035,64 @@ def frame_seal(det, seq, status, record=None):
     return record
 
 
+CALIB_DOUBLES = 36          # per sample: Tr_velo_to_cam 12 | R0_rect 9 | P2 12 | img_w | img_h | pad (include/sassd.h)
+
+
+def frame_annos_bytes(batch, cap_d):
+    """Size of the annotation block of include/sassd.h ("KITTI annotations")."""
+    n = int(_C.lib().sassd_frame_annos_bytes(int(batch), int(cap_d)))
+    if n == 0:
+        raise ValueError("no annotation block for batch %d x capD %d" % (batch, cap_d))
+    return n
+
+
+def frame_record_kitti_bytes(batch, cap_d):
+    """Size of the frame record, layout version 2: the version 1 record, then the annotation block on 8 bytes."""
+    n = int(_C.lib().sassd_frame_record_kitti_bytes(int(batch), int(cap_d)))
+    if n == 0:
+        raise ValueError("no frame record for batch %d x capD %d" % (batch, cap_d))
+    return n
+
+
+def _chk_calib(calib, b):
+    if calib.dtype != torch.float64 or calib.numel() != b * CALIB_DOUBLES or not calib.is_contiguous():
+        raise ValueError("calib must be a contiguous float64 tensor of [%d, %d]" % (b, CALIB_DOUBLES))
+
+
+def frame_annos(det, calib, annos=None):
+    """The detection buffers `det` and the calibration block `calib` ([B, 36] float64) -> the annotation block (uint8 tensor
+    of frame_annos_bytes): kept / index / cam / alpha / bbox of the detections whose projection meets the image.  Reads
+    its inputs, writes the block only; one kernel launch."""
+    boxes, counts = det["boxes"], det["counts"]
+    _chk_cuda(boxes, counts, calib, annos)
+    b, cap_d = int(boxes.shape[0]), int(boxes.shape[1])
+    _chk_calib(calib, b)
+    nbytes = frame_annos_bytes(b, cap_d)
+    if annos is None:
+        annos = torch.empty(nbytes, dtype=torch.uint8, device=boxes.device)
+    rc = _C.lib().sassd_frame_annos(_C.ptr(boxes), _C.ptr(counts), b, cap_d, _C.ptr(calib), _C.ptr(annos),
+                                    annos.numel() * annos.element_size(), _C.stream())
+    _C.check(rc, "sassd_frame_annos")
+    return annos
+
+
+def frame_seal_kitti(det, seq, status, calib, record=None):
+    """frame_seal with the annotation block behind it: the frame record of layout version 2 (uint8 tensor of
+    frame_record_kitti_bytes).  Two kernel launches."""
+    boxes, scores, labels, counts = det["boxes"], det["scores"], det["labels"], det["counts"]
+    _chk_cuda(boxes, scores, labels, counts, seq, status, calib, record)
+    b, cap_d = int(boxes.shape[0]), int(boxes.shape[1])
+    _chk_calib(calib, b)
+    nbytes = frame_record_kitti_bytes(b, cap_d)
+    if record is None:
+        record = torch.empty(nbytes, dtype=torch.uint8, device=boxes.device)
+    rc = _C.lib().sassd_frame_seal_kitti(_C.ptr(boxes), _C.ptr(scores), _C.ptr(labels), _C.ptr(counts), b, cap_d,
+                                         _C.ptr(seq), _C.ptr(status), _C.ptr(calib), _C.ptr(record),
+                                         record.numel() * record.element_size(), _C.stream())
+    _C.check(rc, "sassd_frame_seal_kitti")
+    return record
+
+
 # --------------------------------------------------------------------------------------------------
 def boxes_overlap_bev(a, b, out=None):
     _chk_cuda(a, b)

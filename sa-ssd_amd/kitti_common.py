@@ -201,6 +201,20 @@ def kitti_bbox2results(boxes_lidar, scores, labels, meta, class_names=None):
                 score=np.asarray(scores)[keep], image_idx=np.full(k, int(sample_id), dtype=np.int64))
 
 
+def result_anno_from_cam(cam, scores, labels, sample_idx, class_names):
+    """The annotation kitti_bbox2results returns, from what a FrameStream(annos=True) frame already computed on the GPU:
+    `cam` = dict(index, location, dimensions, rotation_y, alpha, bbox) of the detections whose projection meets the
+    image (sassd.stream.decode_record), `scores` / `labels` of ALL the frame's detections.  Indexing only, no arithmetic."""
+    if cam is None or scores is None or len(cam["index"]) == 0:
+        return empty_result_anno()
+    idx = cam["index"]
+    k = len(idx)
+    return dict(name=np.array([class_names[int(lb)] for lb in np.asarray(labels)[idx]]),
+                truncated=np.zeros(k), occluded=np.zeros(k, dtype=np.int64), alpha=cam["alpha"], bbox=cam["bbox"],
+                dimensions=cam["dimensions"], location=cam["location"], rotation_y=cam["rotation_y"],
+                score=np.asarray(scores)[idx], image_idx=np.full(k, int(sample_idx), dtype=np.int64))
+
+
 # ---- per-frame info records (tools/kitti_common.py:77-213,476-518; consumed by sassd.create_data) ----------------------
 
 def png_shape(path):

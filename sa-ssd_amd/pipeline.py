@@ -651,7 +651,7 @@ class InferencePlan:
             return self._tail(anchors_mask)
 
     # ---- hipGraph: the whole frame as ONE launch ---------------------------------------------------------
-    def capture(self, points_cap, ndim=4, stages=("voxelize", "backbone", "tail"), seal=False, raw_cap=None):
+    def capture(self, points_cap, ndim=4, stages=("voxelize", "backbone", "tail"), seal=False, raw_cap=None, annos=False):
         """Capture the frame (raw points -> detections, side stream included) into a hipGraph.  Input staging:
         `self.pts_in[b]` [points_cap, ndim] f32 and `self.npts` int32 [B]; `run_graph(clouds)` fills them and replays.
         `stages` lets a caller capture a sub-range (e.g. only the sparse backbone for a roofline measurement).
@@ -666,32 +666,47 @@ class InferencePlan:
         (two kernels each), which write `pts_in[b]` and `npts[b]` for the unchanged voxelizer.  A sweep that keeps more than
         points_cap points sets SASSD_ST_POINT_OVERFLOW.  Staging: planes and counts share ONE device block `_stage_block`
         (uint8: [B,6,4] f64 planes first, so they are 8-byte aligned, then the int32 words [seq, nraw[B]] when sealed, else
-        [nraw[B]]), so a frame's small inputs still travel in one copy (sassd.stream.FrameStream)."""
+        [nraw[B]]), so a frame's small inputs still travel in one copy (sassd.stream.FrameStream).
+        annos=True (needs seal=True): the frame's tail is sassd_frame_seal_kitti -- the record is layout version 2, the
+        KITTI annotation block of include/sassd.h behind the version 1 record.  Its input is `self.calib` [B,36] f64
+        (Tr_velo_to_cam 12, R0_rect 9, P2 12, img_w, img_h, one pad per sample), which rides in `_stage_block` in front of the
+        int32 words and after the crop planes when raw_cap is set too: [planes | calib | seq, npts-or-nraw[B]]."""
         dev = self.dev
+        if annos and not seal:
+            raise ValueError("annos=True writes the annotation block into the frame record: it needs seal=True")
         self.pts_cap = int(points_cap)
         self.raw_cap = None if raw_cap is None else int(raw_cap)
         if self.raw_cap is not None and (self.raw_cap < 1 or "voxelize" not in stages):
             raise ValueError("raw_cap must be >= 1 and needs the voxelize stage")
         self.pts_in = [torch.zeros(self.pts_cap, ndim, dtype=torch.float32, device=dev) for _ in range(self.B)]
+        nplane = self.B * 6 * 4 * 8 if self.raw_cap is not None else 0
+        ncal = self.B * K.CALIB_DOUBLES * 8 if annos else 0
+        if nplane or ncal:                      # the float64 inputs first (8-byte aligned), then the int32 words
+            self._stage_block = torch.zeros(nplane + ncal + 4 * (self.B + (1 if seal else 0)), dtype=torch.uint8, device=dev)
+            words = self._stage_block[nplane + ncal:].view(torch.int32)
+            if annos:
+                self.calib = self._stage_block[nplane:nplane + ncal].view(torch.float64).view(self.B, K.CALIB_DOUBLES)
         if self.raw_cap is not None:
             self.raw_in = [torch.zeros(self.raw_cap, ndim, dtype=torch.float32, device=dev) for _ in range(self.B)]
-            nplane = self.B * 6 * 4 * 8
-            self._stage_block = torch.zeros(nplane + 4 * (self.B + (1 if seal else 0)), dtype=torch.uint8, device=dev)
             self.crop_planes = self._stage_block[:nplane].view(torch.float64).view(self.B, 6, 4)
             self.crop_f32_math = False
-            words = self._stage_block[nplane:].view(torch.int32)
             self.npts = torch.zeros(self.B, dtype=torch.int32, device=dev)      # written by the crop, read by the voxelizer
             if seal:
                 self._stage_words = words
                 self._seq, self.nraw = words[:1], words[1:]
             else:
                 self.nraw = words
+        elif annos:
+            self._stage_words = words
+            self._seq, self.npts = words[:1], words[1:]
         elif seal:
             self._stage_words = torch.zeros(1 + self.B, dtype=torch.int32, device=dev)
             self._seq, self.npts = self._stage_words[:1], self._stage_words[1:]
         else:
             self.npts = torch.zeros(self.B, dtype=torch.int32, device=dev)
-        if seal:
+        if annos:
+            self.record = torch.zeros(K.frame_record_kitti_bytes(self.B, self.capD), dtype=torch.uint8, device=dev)
+        elif seal:
             self.record = torch.zeros(K.frame_record_bytes(self.B, self.capD), dtype=torch.uint8, device=dev)
         assert self.prof is None, "per-stage event timing and graph capture exclude each other"
 
@@ -715,7 +730,9 @@ class InferencePlan:
                     self._tail(None)
                 elif self.overlap:
                     torch.cuda.current_stream(self.dev).wait_event(self.mask_ev)      # join the side stream
-                if seal:
+                if annos:
+                    K.frame_seal_kitti(self.det, self._seq, self.status, self.calib, self.record)
+                elif seal:
                     K.frame_seal(self.det, self._seq, self.status, self.record)
 
         # capture needs a non-default stream (the legacy null stream cannot be captured)

@@ -59,7 +59,7 @@ def train_model(model, optimizer, train_loader, lr_scheduler, sync, start_epoch,
 
 
 def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=None, world=None, inflight=0,
-                points_cap=None, raw_prefix=None):
+                points_cap=None, raw_prefix=None, device_annos=False):
     """Run the detector over `dataset` (test mode) -> list of KITTI result annotations in dataset order on every rank
     (this rank's frames are computed here, the others' gathered from their ranks).  `saveto`: also write result files.
     inflight > 0: the frames' raw points go through model.frame_stream(...) with that many frames in flight (1..4) instead of
@@ -70,7 +70,10 @@ def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=N
     sweep to the camera frustum of its own calib and img_shape inside the captured frame, so the annotations are those of
     the velodyne_reduced/ files.  points_cap (the most points a frustum may keep) then defaults to raw_cap: always enough,
     but the voxelizer's tables are sized for a whole sweep -- pass the real bound (KITTI: about a fifth of the sweep) to
-    keep the frame's memory and its fill kernels at the size of the reduced path."""
+    keep the frame's memory and its fill kernels at the size of the reduced path.
+    `device_annos` (with inflight > 0): the stream is built with annos=True and every frame is submitted with its calib and
+    img_shape, so the camera-frame annotation (location, alpha, the clipped 2-D box, the keep test) is computed inside the
+    captured frame and only assembled on the host (kitti_common.result_anno_from_cam); False keeps kitti_bbox2results."""
     if rank is None or world is None:
         rank, _, world = D.env_world() if D.dist.is_initialized() else (0, 0, 1)
     if class_names is not None:
@@ -80,7 +83,9 @@ def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=N
     annos = []
     with torch.no_grad():
         if inflight:
-            annos = _stream_test(model, dataset, mine, workers, inflight, points_cap, raw_prefix)
+            annos = _stream_test(model, dataset, mine, workers, inflight, points_cap, raw_prefix, device_annos)
+        elif device_annos:
+            raise ValueError("device_annos needs inflight > 0 (the annotations are written by the captured frame of a FrameStream)")
         elif raw_prefix is not None:
             raise ValueError("raw_prefix needs inflight > 0 (the crop lives in the captured frame of a FrameStream)")
         else:
@@ -95,7 +100,7 @@ def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=N
     return merged
 
 
-def _stream_test(model, dataset, indices, workers, inflight, points_cap=None, raw_prefix=None):
+def _stream_test(model, dataset, indices, workers, inflight, points_cap=None, raw_prefix=None, device_annos=False):
     """single_test's frames through a FrameStream: the point files are read ahead on `workers` threads, submitted as host
     clouds, and every result becomes the annotation forward_test builds for the frame's img_meta."""
     from concurrent.futures import ThreadPoolExecutor
@@ -120,6 +125,7 @@ def _stream_test(model, dataset, indices, workers, inflight, points_cap=None, ra
     gen = dataset.generator
     fs = model.frame_stream(dataset.anchors, inflight=inflight, points_cap=points_cap, batch_size=1, device=dataset._dev(),
                             **({} if raw_cap is None else dict(raw_cap=raw_cap)),
+                            **(dict(annos=True) if device_annos else {}),
                             anchors_bv=dataset.anchors_bv, voxel_size=tuple(gen.voxel_size),
                             point_cloud_range=tuple(gen.point_cloud_range), max_num_points=gen.max_num_points_per_voxel,
                             max_voxels=gen._max_voxels, anchor_area_threshold=dataset.anchor_area_threshold)
@@ -136,10 +142,13 @@ def _stream_test(model, dataset, indices, workers, inflight, points_cap=None, ra
                         pending.append(pool.submit(load[0], indices[nxt], *load[1:]))
                         nxt += 1
                     metas.append(dict(img_shape=fr['img_shape'], sample_idx=fr['sample_idx'], calib=fr['calib']))
-                    if raw_prefix is None:
-                        yield [fr['points']]
+                    view = [dict(calib=fr['calib'], img_shape=fr['img_shape'])]
+                    if raw_prefix is not None:          # a raw stream's dict frustums serve as its calibs too
+                        yield [fr['points']], view
+                    elif device_annos:
+                        yield [fr['points']], None, view
                     else:
-                        yield [fr['points']], [dict(calib=fr['calib'], img_shape=fr['img_shape'])]
+                        yield [fr['points']]
             for _, dets in fs.map(batches()):
                 annos += model.result_annos(dets, [metas.popleft()])
     finally:

@@ -22,19 +22,29 @@ Raw sweeps: FrameStream(..., raw_cap=122880) puts the camera-frustum reduction (
 captured frame -- sassd_crop_polytope_dev, two kernels per sample in front of the voxelizer.  submit(clouds, frustums) then
 takes clouds of up to raw_cap points and one frustum per cloud ([6,4] float64 planes of geometry.frustum_planes, or
 dict(calib=..., img_shape=...)); the planes ride in the staging block of the counts: [planes[B,6,4] f64 | seq, nraw[B]].
+
+KITTI annotations: FrameStream(..., annos=True) ends the frame with sassd_frame_seal_kitti -- the record is layout version
+2, the version 1 record plus the annotation block (camera-frame boxes, alpha, clipped 2-D boxes of the detections whose
+projection meets the image).  submit(clouds, frustums, calibs) then takes one dict(calib=..., img_shape=...) per cloud; the
+[B,36] float64 calibration block rides in the same staging block, behind the planes.  collect() returns per sample
+(boxes, scores, labels, cam); kitti_common.result_anno_from_cam turns `cam` into the result annotation by indexing alone.
 """
 from collections import deque
 
 import numpy as np
 
 FRAME_MAGIC = 0x53460001            # SASSD_FRAME_MAGIC: 'S' 'F', layout version 1
+FRAME_MAGIC_KITTI = 0x53460002      # SASSD_FRAME_MAGIC_KITTI: layout version 2, the annotation block behind the v1 record
+CALIB_DOUBLES = 36                  # per sample: Tr_velo_to_cam 12 | R0_rect 9 | P2 12 | img_w | img_h | pad
 MAX_INFLIGHT = 4                    # one HIP stream per frame in flight; the runtime multiplexes a process onto 4 hardware queues
 _SEQ_MASK = 0x7FFFFFFF
 
 
-def record_layout(B, capD):
+def record_layout(B, capD, annos=False):
     """Byte offsets of the frame record for `B` samples x `capD` detection rows (include/sassd.h "Frame record"):
-    dict(magic, seq, status, B, capD, counts, boxes, scores, labels, total) -- every field 4-byte aligned, in this order."""
+    dict(magic, seq, status, B, capD, counts, boxes, scores, labels, total) -- every field 4-byte aligned, in this order.
+    annos=True: layout version 2 -- the same offsets, then the annotation block ("KITTI annotations") at the next 8-byte
+    boundary: annos (its start), kept, index, cam, alpha, bbox (8-byte aligned), and the new total."""
     B, capD = int(B), int(capD)
     if B < 1 or capD < 1 or B * capD > (1 << 24):
         raise ValueError("no frame record for batch %d x capD %d" % (B, capD))
@@ -43,8 +53,15 @@ def record_layout(B, capD):
     boxes = 4 * hdr
     scores = boxes + 4 * 7 * n
     labels = scores + 4 * n
-    return dict(magic=0, seq=4, status=8, B=12, capD=16, counts=20, boxes=boxes, scores=scores, labels=labels,
-                total=labels + 4 * n)
+    L = dict(magic=0, seq=4, status=8, B=12, capD=16, counts=20, boxes=boxes, scores=scores, labels=labels,
+             total=labels + 4 * n)
+    if annos:
+        at = (L["total"] + 7) // 8 * 8
+        index = at + 4 * ((B + 1) // 2 * 2)         # kept[B], one zero word when B is odd
+        alpha = index + 4 * n + 28 * n
+        bbox = alpha + 4 * n + 4 * (n & 1)          # one zero word when n is odd
+        L.update(annos=at, kept=at, index=index, cam=index + 4 * n, alpha=alpha, bbox=bbox, total=bbox + 32 * n)
+    return L
 
 
 class FrameStatusError(RuntimeError):
@@ -71,11 +88,9 @@ def _extend4(m):
     return out
 
 
-def frustum_of(calib, img_shape):
-    """The [6,4] float64 planes of a frame's camera-2 viewing frustum (geometry.frustum_planes) from its calibration -- a
-    kitti_common.Calibration (P2, R0, V2C) or a dict with P2, R0_rect, Tr_velo_to_cam (3x3 / 3x4 / 4x4, or the flat rows
-    of a KITTI calib file) -- and its image shape (h, w).  Host arithmetic only."""
-    from .geometry import frustum_planes
+def _calib_matrices(calib):
+    """(P2, R0_rect, Tr_velo_to_cam) as float64 matrices from a kitti_common.Calibration or a dict of them (the forms of
+    frustum_of): flat rows of a KITTI calib file are reshaped, 3x3 / 3x4 / 4x4 are taken as they are."""
     if isinstance(calib, dict):
         get = lambda *ks: next(calib[k] for k in ks if k in calib)      # noqa: E731
         p2, r0, v2c = get("P2", "calib/P2"), get("R0_rect", "calib/R0_rect"), get("Tr_velo_to_cam", "calib/Tr_velo_to_cam")
@@ -88,16 +103,74 @@ def frustum_of(calib, img_shape):
         r0 = r0.reshape(3, 3)
     if v2c.ndim == 1:
         v2c = v2c.reshape(3, 4)
+    return p2, r0, v2c
+
+
+def calib_block_of(calib, img_shape):
+    """One sample's calibration block for the annotation kernel (include/sassd.h "KITTI annotations"): [36] float64 --
+    Tr_velo_to_cam [3,4], R0_rect [3,3], P2 [3,4], img_w, img_h, 0 -- from the forms frustum_of accepts.  ValueError for a
+    matrix that is not finite or an image size that is not positive."""
+    p2, r0, v2c = _calib_matrices(calib)
+    h, w = int(img_shape[0]), int(img_shape[1])
+    if h < 1 or w < 1:
+        raise ValueError("img_shape must be positive, got %s" % (tuple(img_shape),))
+    out = np.zeros(CALIB_DOUBLES)
+    out[:12], out[12:21], out[21:33] = v2c[:3, :4].ravel(), r0[:3, :3].ravel(), p2[:3, :4].ravel()
+    out[33], out[34] = w, h
+    if not np.isfinite(out).all():
+        raise ValueError("calibration matrices must be finite")
+    return out
+
+
+def frustum_of(calib, img_shape):
+    """The [6,4] float64 planes of a frame's camera-2 viewing frustum (geometry.frustum_planes) from its calibration -- a
+    kitti_common.Calibration (P2, R0, V2C) or a dict with P2, R0_rect, Tr_velo_to_cam (3x3 / 3x4 / 4x4, or the flat rows
+    of a KITTI calib file) -- and its image shape (h, w).  Host arithmetic only."""
+    from .geometry import frustum_planes
+    p2, r0, v2c = _calib_matrices(calib)
     planes, f32 = frustum_planes(_extend4(r0), _extend4(v2c), _extend4(p2), (int(img_shape[0]), int(img_shape[1])))
     assert not f32                                  # float64 calibration gives float64 planes: the stream's crop is float64
     return planes
 
 
-def check_frame_inputs(clouds, frustums, B, ndim, points_cap, raw_cap=None):
+def _check_calibs(calibs, frustums, B, annos):
+    """The calibration side of check_frame_inputs -> [B,36] float64, or None on a stream without annos."""
+    if not annos:
+        if calibs is not None:
+            raise ValueError("calibs given to a stream without annos (its record holds lidar-frame detections only)")
+        return None
+    if calibs is None and frustums is not None and len(frustums) == B and all(isinstance(f, dict) for f in frustums):
+        calibs = frustums                       # a raw stream fed with dict(calib=, img_shape=): the same dicts serve both
+    if calibs is None:
+        raise ValueError("a stream with annos projects every detection: submit(..., calibs=) needs one "
+                         "dict(calib=, img_shape=) per cloud")
+    if len(calibs) != B:
+        raise ValueError("%d calibs for a stream of batch_size %d" % (len(calibs), B))
+    out = np.empty((B, CALIB_DOUBLES), dtype=np.float64)
+    for b, c in enumerate(calibs):
+        if not isinstance(c, dict) or c.get("calib") is None or c.get("img_shape") is None:
+            raise ValueError("calib %d: a dict with `calib` and `img_shape` is needed" % b)
+        try:
+            out[b] = calib_block_of(c["calib"], c["img_shape"])
+        except ValueError as e:
+            raise ValueError("calib %d: %s" % (b, e)) from None
+    return out
+
+
+def check_frame_inputs(clouds, frustums, B, ndim, points_cap, raw_cap=None, calibs=None, annos=False):
     """The checks a slot makes on one frame's inputs before it queues anything (host only).  ValueError for: the wrong
     number of clouds, a cloud that is not [N, ndim], a cloud above the stream's capacity (raw_cap on a raw stream, else
     points_cap), frustums missing on a raw stream or given to a stream without raw_cap, the wrong number of frustums,
-    planes that are not [6,4] or not finite.  -> the planes as one [B,6,4] float64 array, or None without raw_cap."""
+    planes that are not [6,4] or not finite.  -> the planes as one [B,6,4] float64 array, or None without raw_cap.
+    With annos=True (a stream that writes KITTI annotations) also: calibs missing (unless the frustums are
+    dict(calib=, img_shape=), which then serve as calibs too) or miscounted, a non-finite calibration matrix, a non-positive
+    image size -> (planes, the [B,36] float64 calibration block).  calibs given with annos=False is a ValueError too."""
+    planes = _check_clouds_and_frustums(clouds, frustums, B, ndim, points_cap, raw_cap)
+    block = _check_calibs(calibs, frustums, B, annos)
+    return (planes, block) if annos else planes
+
+
+def _check_clouds_and_frustums(clouds, frustums, B, ndim, points_cap, raw_cap):
     if len(clouds) != B:
         raise ValueError("a batch of %d clouds for a stream of batch_size %d" % (len(clouds), B))
     cap, what = (points_cap, "points_cap") if raw_cap is None else (raw_cap, "raw_cap")
@@ -129,18 +202,22 @@ def check_frame_inputs(clouds, frustums, B, ndim, points_cap, raw_cap=None):
     return out
 
 
-def decode_record(buf, B, capD, seq):
+def decode_record(buf, B, capD, seq, annos=False):
     """One frame record (bytes-like / uint8 array of record_layout(B, capD)['total'] bytes) -> what plan.results() returns:
     per sample (boxes [k,7] f32, scores [k] f32, labels [k] i64), or (None, None, None) for a sample without detections.
     The arrays are copies.  RuntimeError("stale frame record") unless the record carries the magic word, this B / capD and
-    `seq`; the status error of plan.results() when its status word is not zero."""
-    L = record_layout(B, capD)
+    `seq`; the status error of plan.results() when its status word is not zero.
+    annos=True: a record of layout version 2 (its magic word is checked instead) -> per sample (boxes, scores, labels, cam),
+    cam = dict(index i64[k'], location f32[k',3], dimensions f32[k',3], rotation_y f32[k'], alpha f32[k'], bbox f64[k',4])
+    of the k' detections whose projection meets the image (`index`: their rows in boxes), all copies; (None,) * 4 for a
+    sample without detections, zero-length arrays when every detection missed the image."""
+    L = record_layout(B, capD, annos)
     if memoryview(buf).nbytes < L["total"]:
         raise RuntimeError("stale frame record")
     raw = np.frombuffer(buf, dtype=np.uint8, count=L["total"])
     words = raw.view(np.int32)
     n = B * capD
-    if (int(words[0]) != FRAME_MAGIC or int(words[3]) != B or int(words[4]) != capD
+    if (int(words[0]) != (FRAME_MAGIC_KITTI if annos else FRAME_MAGIC) or int(words[3]) != B or int(words[4]) != capD
             or int(words[1]) != (int(seq) & _SEQ_MASK)):
         raise RuntimeError("stale frame record")
     st = int(words[2])
@@ -150,13 +227,25 @@ def decode_record(buf, B, capD, seq):
     boxes = raw[L["boxes"]:L["scores"]].view(np.float32).reshape(B, capD, 7)
     scores = raw[L["scores"]:L["labels"]].view(np.float32).reshape(B, capD)
     labels = words[L["labels"] // 4:L["labels"] // 4 + n].reshape(B, capD)
+    if annos:
+        kept = words[L["kept"] // 4:L["kept"] // 4 + B]
+        index = words[L["index"] // 4:L["index"] // 4 + n].reshape(B, capD)
+        cam = raw[L["cam"]:L["alpha"]].view(np.float32).reshape(B, capD, 7)
+        alpha = raw[L["alpha"]:L["alpha"] + 4 * n].view(np.float32).reshape(B, capD)
+        bbox = raw[L["bbox"]:L["total"]].view(np.float64).reshape(B, capD, 4)
     out = []
     for b in range(B):
         k = min(max(int(counts[b]), 0), capD)
         if k == 0:
-            out.append((None, None, None))
-        else:
-            out.append((boxes[b, :k].copy(), scores[b, :k].copy(), labels[b, :k].astype(np.int64)))
+            out.append((None,) * (4 if annos else 3))
+            continue
+        det = (boxes[b, :k].copy(), scores[b, :k].copy(), labels[b, :k].astype(np.int64))
+        if annos:
+            m = min(max(int(kept[b]), 0), k)
+            det += (dict(index=index[b, :m].astype(np.int64), location=cam[b, :m, :3].copy(),
+                         dimensions=cam[b, :m, 3:6].copy(), rotation_y=cam[b, :m, 6].copy(), alpha=alpha[b, :m].copy(),
+                         bbox=bbox[b, :m].copy()),)
+        out.append(det)
     return out
 
 
@@ -164,7 +253,8 @@ class FrameRing:
     """Tickets over a ring of slots.  Ticket t (1, 2, ...) runs on slot (t - 1) % len(slots); a slot is
 
         stage(seq, clouds)   check and queue the inputs of one frame (ValueError for inputs it cannot take: nothing queued);
-                             called as stage(seq, clouds, frustums) when submit() was given frustums, and only then
+                             called as stage(seq, clouds, frustums) when submit() was given frustums, and only then;
+                             with calibs=<calibs> as a keyword when submit() was given calibs, and only then
         launch()             queue the frame and the copy of its record
         ready() / wait()     has the record arrived / block until it has
         record()             the arrived record, valid until the next stage()
@@ -199,17 +289,16 @@ class FrameRing:
                 recover()
         self.busy[i] = None
 
-    def submit(self, clouds, frustums=None):
+    def submit(self, clouds, frustums=None, calibs=None):
         if self.closed:
             raise RuntimeError("FrameStream is closed")
         t = self.next_ticket
         i = (t - 1) % len(self.slots)
         if self.busy[i] is not None:
             self._harvest(i)
-        if frustums is None:
-            self.slots[i].stage(t & _SEQ_MASK, clouds)     # a ValueError leaves the ticket unused and the slot free
-        else:
-            self.slots[i].stage(t & _SEQ_MASK, clouds, frustums)
+        args = (clouds,) if frustums is None else (clouds, frustums)
+        kw = {} if calibs is None else dict(calibs=calibs)
+        self.slots[i].stage(t & _SEQ_MASK, *args, **kw)    # a ValueError leaves the ticket unused and the slot free
         self.slots[i].launch()
         self.busy[i] = t
         self.next_ticket = t + 1
@@ -240,7 +329,8 @@ class FrameRing:
 
     def map(self, batches):
         """(ticket, result) per batch of `batches`, in order, with at most len(slots) frames submitted and not yet yielded.
-        A batch is a list of clouds, or the tuple (clouds, frustums) for a stream with raw_cap."""
+        A batch is a list of clouds, or the tuple (clouds, frustums) for a stream with raw_cap, or the tuple
+        (clouds, frustums-or-None, calibs) for a stream with annos."""
         pending = deque()
         try:
             batches = iter(batches)
@@ -252,7 +342,7 @@ class FrameRing:
                     clouds = next(batches)
                 except StopIteration:
                     break
-                if isinstance(clouds, tuple):           # (clouds, frustums): a raw stream's batch
+                if isinstance(clouds, tuple):           # (clouds, frustums[, calibs]): a raw / annos stream's batch
                     pending.append(self.submit(*clouds))
                 else:
                     pending.append(self.submit(clouds))
@@ -280,37 +370,48 @@ class _PlanSlot:
     """One frame in flight: an InferencePlan captured with the seal as its last node, its HIP stream, a pinned staging block
     [seq, npts[B] | B x points_cap x ndim f32], a pinned record buffer and the event behind the record's copy.
     With raw_cap the frame crops: the block is [planes[B,6,4] f64 | seq, nraw[B] | B x raw_cap x ndim f32], the clouds go
-    to plan.raw_in and the plan's first nodes cut them down to points_cap rows of plan.pts_in."""
+    to plan.raw_in and the plan's first nodes cut them down to points_cap rows of plan.pts_in.  With annos the block
+    carries the calibration too, [planes | calib[B,36] f64 | seq, n[B]], and the record is layout version 2."""
 
-    def __init__(self, plan, points_cap, ndim, raw_cap=None):
+    def __init__(self, plan, points_cap, ndim, raw_cap=None, annos=False):
         import torch
         self.torch, self.plan = torch, plan
         dev, B = plan.dev, plan.B
         self.stream = torch.cuda.Stream(device=dev)
         with torch.cuda.stream(self.stream):
-            plan.capture(points_cap, ndim=ndim, seal=True, raw_cap=raw_cap)
+            plan.capture(points_cap, ndim=ndim, seal=True, raw_cap=raw_cap, **(dict(annos=True) if annos else {}))
         self.stream.synchronize()
         self.cap, self.ndim = int(points_cap), int(ndim)
         self.raw_cap = None if raw_cap is None else int(raw_cap)
+        self.annos = bool(annos)
+        self.blocked = self.raw_cap is not None or self.annos
         nwords = 1 + B
-        if self.raw_cap is None:
+        if not self.blocked:
             self.pin_words = torch.zeros(nwords, dtype=torch.int32).pin_memory()
-            self.dev_words, self.dev_pts, rows = plan._stage_words, plan.pts_in, self.cap
-        else:                                   # one pinned block shaped like plan._stage_block: planes, then the words
+            self.dev_words = plan._stage_words
+        else:                       # one pinned block shaped like plan._stage_block: planes, calibration, then the words
             self.pin_block = torch.zeros(plan._stage_block.numel(), dtype=torch.uint8).pin_memory()
-            nplane = B * 6 * 4 * 8
-            self.np_planes = self.pin_block[:nplane].view(torch.float64).view(B, 6, 4).numpy()
-            self.pin_words = self.pin_block[nplane:].view(torch.int32)
-            self.dev_words, self.dev_pts, rows = plan._stage_block, plan.raw_in, self.raw_cap
+            nplane = B * 6 * 4 * 8 if self.raw_cap is not None else 0
+            ncal = B * CALIB_DOUBLES * 8 if self.annos else 0
+            if nplane:
+                self.np_planes = self.pin_block[:nplane].view(torch.float64).view(B, 6, 4).numpy()
+            if ncal:
+                self.np_calib = self.pin_block[nplane:nplane + ncal].view(torch.float64).view(B, CALIB_DOUBLES).numpy()
+            self.pin_words = self.pin_block[nplane + ncal:].view(torch.int32)
+            self.dev_words = plan._stage_block
+        self.dev_pts, rows = (plan.pts_in, self.cap) if self.raw_cap is None else (plan.raw_in, self.raw_cap)
         self.pin_pts = torch.zeros(B, rows, self.ndim, dtype=torch.float32).pin_memory()
         self.pin_rec = torch.zeros(plan.record.numel(), dtype=torch.uint8).pin_memory()
         self.np_words, self.np_pts, self.np_rec = self.pin_words.numpy(), self.pin_pts.numpy(), self.pin_rec.numpy()
         self.event = torch.cuda.Event()
         self.feed = torch.cuda.Event()          # orders device-tensor clouds (produced on the caller's stream) before their copy
 
-    def stage(self, seq, clouds, frustums=None):
+    def stage(self, seq, clouds, frustums=None, calibs=None):
         torch, plan = self.torch, self.plan
-        planes = check_frame_inputs(clouds, frustums, plan.B, self.ndim, self.cap, self.raw_cap)   # nothing is queued before this
+        planes = check_frame_inputs(clouds, frustums, plan.B, self.ndim, self.cap, self.raw_cap, calibs,
+                                    self.annos)                                              # nothing is queued before this
+        if self.annos:
+            planes, self.np_calib[...] = planes
         if planes is not None:
             self.np_planes[...] = planes
         on_dev = [torch.is_tensor(p) and p.is_cuda for p in clouds]
@@ -331,7 +432,7 @@ class _PlanSlot:
                 else:
                     self.np_pts[b, :n] = pts.numpy() if torch.is_tensor(pts) else pts
                     self.dev_pts[b][:n].copy_(self.pin_pts[b, :n], non_blocking=True)
-            self.dev_words.copy_(self.pin_words if self.raw_cap is None else self.pin_block, non_blocking=True)
+            self.dev_words.copy_(self.pin_block if self.blocked else self.pin_words, non_blocking=True)
 
     def launch(self):
         torch = self.torch
@@ -379,12 +480,19 @@ class FrameStream:
     detects on the kept points exactly as if they had been submitted to a stream without raw_cap; a frame that keeps more
     than points_cap points raises FrameStatusError with SASSD_ST_POINT_OVERFLOW (16) from its collect().  A cloud above
     raw_cap, missing / miscounted frustums, planes that are not [6,4] float64 or not finite, and frustums given to a stream
-    without raw_cap raise ValueError at submit, before anything is queued.  A frame whose status word is not zero raises plan.results()'s
+    without raw_cap raise ValueError at submit, before anything is queued.  With `annos=True` the frame
+    also writes the KITTI result annotation of its detections (include/sassd.h "KITTI annotations"):
+    submit(clouds, frustums, calibs) takes one dict(calib=<kitti_common.Calibration or dict of P2 / R0_rect /
+    Tr_velo_to_cam>, img_shape=(h, w[, c])) per cloud -- on a raw stream whose frustums are such dicts, calibs defaults to
+    them -- and collect() returns per sample (boxes, scores, labels, cam), cam as decode_record(annos=True) documents it
+    (kitti_common.result_anno_from_cam builds the annotation from it).  Missing / miscounted calibs, a non-finite matrix, a
+    non-positive image size, and calibs given to a stream without annos raise ValueError at submit, before anything is
+    queued.  A frame whose status word is not zero raises plan.results()'s
     RuntimeError from ITS collect(); a record that is not the ticket's own raises RuntimeError("stale frame record").
     `plans` are the InferencePlans (for tools); plan_kwargs go to InferencePlan (precision, sparse_precision, ...)."""
 
     def __init__(self, state_dict, inflight=3, points_cap=None, batch_size=1, anchors=None, device=None, ndim=4,
-                 raw_cap=None, **plan_kwargs):
+                 raw_cap=None, annos=False, **plan_kwargs):
         from .pipeline import InferencePlan
         inflight = int(inflight)
         if not 1 <= inflight <= MAX_INFLIGHT:
@@ -397,14 +505,15 @@ class FrameStream:
             raise ValueError("raw_cap (the largest raw sweep the stream accepts) must be >= 1")
         self.inflight, self.points_cap, self.batch_size = inflight, int(points_cap), int(batch_size)
         self.raw_cap = None if raw_cap is None else int(raw_cap)
+        self.annos = bool(annos)
         self.plans = [InferencePlan(state_dict, batch_size=batch_size, anchors=anchors, device=device,
                                     overlap=inflight == 1, **plan_kwargs) for _ in range(inflight)]
         B, capD = self.plans[0].B, self.plans[0].capD
-        self._slots = [_PlanSlot(p, self.points_cap, ndim, self.raw_cap) for p in self.plans]
-        self._ring = FrameRing(self._slots, lambda rec, seq: decode_record(rec, B, capD, seq))
+        self._slots = [_PlanSlot(p, self.points_cap, ndim, self.raw_cap, self.annos) for p in self.plans]
+        self._ring = FrameRing(self._slots, lambda rec, seq: decode_record(rec, B, capD, seq, self.annos))
 
-    def submit(self, clouds, frustums=None):
-        return self._ring.submit(clouds, frustums)
+    def submit(self, clouds, frustums=None, calibs=None):
+        return self._ring.submit(clouds, frustums, calibs)
 
     def collect(self, ticket):
         return self._ring.collect(ticket)
