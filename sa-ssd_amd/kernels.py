@@ -1035,9 +1035,6 @@ def frame_seal(det, seq, status, record=None):
     return record
 
 
-CALIB_DOUBLES = 36          # per sample: Tr_velo_to_cam 12 | R0_rect 9 | P2 12 | img_w | img_h | pad (include/sassd.h)
-
-
 def frame_annos_bytes(batch, cap_d):
     """Size of the annotation block of include/sassd.h ("KITTI annotations")."""
     n = int(_C.lib().sassd_frame_annos_bytes(int(batch), int(cap_d)))
@@ -1055,6 +1052,7 @@ def frame_record_kitti_bytes(batch, cap_d):
 
 
 def _chk_calib(calib, b):
+    from .stream import CALIB_DOUBLES       # stated once, there; imported here so that the plain paths never load the stream module
     if calib.dtype != torch.float64 or calib.numel() != b * CALIB_DOUBLES or not calib.is_contiguous():
         raise ValueError("calib must be a contiguous float64 tensor of [%d, %d]" % (b, CALIB_DOUBLES))
 

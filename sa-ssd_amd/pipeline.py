@@ -39,6 +39,7 @@ import torch
 
 from . import kernels as K
 from . import anchors as A
+from .stream import CALIB_DOUBLES, stage_layout
 
 BN_EPS = 1e-3
 
@@ -211,6 +212,8 @@ class InferencePlan:
         self.spconv_cfg, self.wino4_cfg = spconv_cfg, wino4_cfg
         self.graph = None
         self.record = None         # device frame record: capture(seal=True)
+        self.raw_cap = None        # capture(raw_cap=...): the frame crops raw sweeps
+        self._stage_block = None   # capture(): the frame's small inputs in one device block (sassd.stream.stage_layout)
         self._wsid = id(self)
         # coordinate-only work (rulebooks, anchors_mask) runs on a side stream, overlapping the feature path
         self.overlap = bool(overlap)
@@ -655,22 +658,21 @@ class InferencePlan:
         """Capture the frame (raw points -> detections, side stream included) into a hipGraph.  Input staging:
         `self.pts_in[b]` [points_cap, ndim] f32 and `self.npts` int32 [B]; `run_graph(clouds)` fills them and replays.
         `stages` lets a caller capture a sub-range (e.g. only the sparse backbone for a roofline measurement).
+        Staging: the frame's small inputs -- crop planes, calibration, seq, counts -- are views into ONE device block,
+        `self._stage_block` (uint8), cut by sassd.stream.stage_layout(B, raw_cap is not None, annos, seal), so that they
+        travel in one copy (sassd.stream.FrameStream).
         seal=True: the frame's last node is sassd_frame_seal -- `self.record` (device uint8) then holds the frame record of
-        include/sassd.h after every replay, its `seq` word echoed from a device word, which shares one int32 block
-        [seq, npts[B]] with `self.npts` so that both are staged in one copy (sassd.stream.FrameStream).
+        include/sassd.h after every replay, its `seq` word echoed from the device word `self._seq`.
         The launch sequence that was captured stays on the plan as `_frame_fn`, for inspection only (a test captures it once
         more into a plain hipGraph to count its node types); nothing on the frame path calls it.
         raw_cap: the frame starts at a raw sweep.  Its input is `self.raw_in[b]` [raw_cap, ndim] f32, `self.nraw` int32 [B] and
         `self.crop_planes` [B,6,4] f64 (`self.crop_f32_math`, a host flag read at capture, says how they are evaluated:
         False, the float64 test of geometry.frustum_planes); its first nodes are one sassd_crop_polytope_dev per sample
         (two kernels each), which write `pts_in[b]` and `npts[b]` for the unchanged voxelizer.  A sweep that keeps more than
-        points_cap points sets SASSD_ST_POINT_OVERFLOW.  Staging: planes and counts share ONE device block `_stage_block`
-        (uint8: [B,6,4] f64 planes first, so they are 8-byte aligned, then the int32 words [seq, nraw[B]] when sealed, else
-        [nraw[B]]), so a frame's small inputs still travel in one copy (sassd.stream.FrameStream).
+        points_cap points sets SASSD_ST_POINT_OVERFLOW.  The block's counts are then `nraw`; `npts` is a tensor of its own.
         annos=True (needs seal=True): the frame's tail is sassd_frame_seal_kitti -- the record is layout version 2, the
         KITTI annotation block of include/sassd.h behind the version 1 record.  Its input is `self.calib` [B,36] f64
-        (Tr_velo_to_cam 12, R0_rect 9, P2 12, img_w, img_h, one pad per sample), which rides in `_stage_block` in front of the
-        int32 words and after the crop planes when raw_cap is set too: [planes | calib | seq, npts-or-nraw[B]]."""
+        (Tr_velo_to_cam 12, R0_rect 9, P2 12, img_w, img_h, one pad per sample)."""
         dev = self.dev
         if annos and not seal:
             raise ValueError("annos=True writes the annotation block into the frame record: it needs seal=True")
@@ -679,31 +681,21 @@ class InferencePlan:
         if self.raw_cap is not None and (self.raw_cap < 1 or "voxelize" not in stages):
             raise ValueError("raw_cap must be >= 1 and needs the voxelize stage")
         self.pts_in = [torch.zeros(self.pts_cap, ndim, dtype=torch.float32, device=dev) for _ in range(self.B)]
-        nplane = self.B * 6 * 4 * 8 if self.raw_cap is not None else 0
-        ncal = self.B * K.CALIB_DOUBLES * 8 if annos else 0
-        if nplane or ncal:                      # the float64 inputs first (8-byte aligned), then the int32 words
-            self._stage_block = torch.zeros(nplane + ncal + 4 * (self.B + (1 if seal else 0)), dtype=torch.uint8, device=dev)
-            words = self._stage_block[nplane + ncal:].view(torch.int32)
-            if annos:
-                self.calib = self._stage_block[nplane:nplane + ncal].view(torch.float64).view(self.B, K.CALIB_DOUBLES)
+        L = stage_layout(self.B, self.raw_cap is not None, annos, seal)
+        block = self._stage_block = torch.zeros(L["total"], dtype=torch.uint8, device=dev)
+        counts = block[L["counts"]:L["total"]].view(torch.int32)
+        if seal:
+            self._seq = block[L["seq"]:L["counts"]].view(torch.int32)
+        if annos:
+            self.calib = block[L["calib"]:L["words"]].view(torch.float64).view(self.B, CALIB_DOUBLES)
         if self.raw_cap is not None:
             self.raw_in = [torch.zeros(self.raw_cap, ndim, dtype=torch.float32, device=dev) for _ in range(self.B)]
-            self.crop_planes = self._stage_block[:nplane].view(torch.float64).view(self.B, 6, 4)
+            self.crop_planes = block[L["planes"]:L["calib"]].view(torch.float64).view(self.B, 6, 4)
             self.crop_f32_math = False
+            self.nraw = counts
             self.npts = torch.zeros(self.B, dtype=torch.int32, device=dev)      # written by the crop, read by the voxelizer
-            if seal:
-                self._stage_words = words
-                self._seq, self.nraw = words[:1], words[1:]
-            else:
-                self.nraw = words
-        elif annos:
-            self._stage_words = words
-            self._seq, self.npts = words[:1], words[1:]
-        elif seal:
-            self._stage_words = torch.zeros(1 + self.B, dtype=torch.int32, device=dev)
-            self._seq, self.npts = self._stage_words[:1], self._stage_words[1:]
         else:
-            self.npts = torch.zeros(self.B, dtype=torch.int32, device=dev)
+            self.npts = counts
         if annos:
             self.record = torch.zeros(K.frame_record_kitti_bytes(self.B, self.capD), dtype=torch.uint8, device=dev)
         elif seal:
@@ -750,7 +742,7 @@ class InferencePlan:
         return self.graph
 
     def stage_inputs(self, clouds):
-        if getattr(self, "raw_cap", None) is not None:
+        if self.raw_cap is not None:
             raise RuntimeError("a plan captured with raw_cap is fed through raw_in / nraw / crop_planes (sassd.stream.FrameStream)")
         for b, pts in enumerate(clouds or ()):
             n = pts.shape[0]

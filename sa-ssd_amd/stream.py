@@ -4,14 +4,15 @@ The rate README publishes for car_cfg batch 1 comes from three one-branch frame 
 round-robin on three HIP streams.  This module is that recipe behind a public call, with what a user
 needs added: the result leaves the GPU.  Per frame and slot:
 
-  submit   pinned staging block [seq, npts[B] | points] -> one H2D copy per cloud + one for the int block (no fill launches)
+  submit   pinned clouds + staging block -> one H2D copy per cloud + one for the block of `stage_layout` (no fill launches)
            graph.launch()            the captured frame; its last node, sassd_frame_seal, writes the frame record
            one D2H copy              the record -> a pinned host buffer; an event behind it
   collect  event.synchronize()       then decode the record: magic, seq == ticket, status, counts, boxes / scores / labels
 
 The record layout is the contract of include/sassd.h ("Frame record"); `record_layout` is its only Python statement and the
-decoder reads nothing else.  Ring order, back-pressure and the error rules live in `FrameRing`, which drives any "slot" with
-stage / launch / ready / wait / record -- the CPU tests hand it a fake one.
+decoder reads nothing else.  `stage_layout` is the same for the frame's small inputs: InferencePlan.capture() cuts the
+device block by it, the slot its pinned twin.  Ring order, back-pressure and the error rules live in `FrameRing`, which
+drives any "slot" with stage / launch / ready / wait / record -- the CPU tests hand it a fake one.
 
     fs = FrameStream(state_dict, inflight=3, points_cap=21504, batch_size=1, anchors=an, device=dev)
     for ticket, dets in fs.map(batches):     # dets: what plan.results() returns for that batch
@@ -21,7 +22,7 @@ stage / launch / ready / wait / record -- the CPU tests hand it a fake one.
 Raw sweeps: FrameStream(..., raw_cap=122880) puts the camera-frustum reduction (velodyne -> velodyne_reduced) into the
 captured frame -- sassd_crop_polytope_dev, two kernels per sample in front of the voxelizer.  submit(clouds, frustums) then
 takes clouds of up to raw_cap points and one frustum per cloud ([6,4] float64 planes of geometry.frustum_planes, or
-dict(calib=..., img_shape=...)); the planes ride in the staging block of the counts: [planes[B,6,4] f64 | seq, nraw[B]].
+dict(calib=..., img_shape=...)); the planes ride in the staging block of the counts (`stage_layout`).
 
 KITTI annotations: FrameStream(..., annos=True) ends the frame with sassd_frame_seal_kitti -- the record is layout version
 2, the version 1 record plus the annotation block (camera-frame boxes, alpha, clipped 2-D boxes of the detections whose
@@ -62,6 +63,31 @@ def record_layout(B, capD, annos=False):
         bbox = alpha + 4 * n + 4 * (n & 1)          # one zero word when n is odd
         L.update(annos=at, kept=at, index=index, cam=index + 4 * n, alpha=alpha, bbox=bbox, total=bbox + 32 * n)
     return L
+
+
+def stage_layout(B, raw=False, annos=False, seal=False):
+    """Byte offsets of the frame's staging block -- its small per-frame inputs, one H2D copy -- for `B` samples:
+    dict(planes, calib, words, seq, counts, total), in this order: the crop planes [B,6,4] f64 (`raw`: a frame that crops raw
+    sweeps), the calibration block [B,CALIB_DOUBLES] f64 (`annos`), then the int32 words: [seq] when `seal`, counts[B] (the
+    points per cloud).  A part that is absent has length 0; `seq` is None when not sealed.  The float64 parts come first, so
+    they are 8-byte aligned."""
+    B = int(B)
+    if B < 1:
+        raise ValueError("no staging block for batch %d" % B)
+    calib = 8 * 6 * 4 * B if raw else 0
+    words = calib + (8 * CALIB_DOUBLES * B if annos else 0)
+    counts = words + (4 if seal else 0)
+    return dict(planes=0, calib=calib, words=words, seq=words if seal else None, counts=counts, total=counts + 4 * B)
+
+
+def stage_views(buf, B, L):
+    """numpy views into `buf` (uint8, at least L['total'] bytes) of the parts of L = stage_layout(B, ...):
+    dict(planes [B,6,4] f64 | None, calib [B,CALIB_DOUBLES] f64 | None, seq [1] i32 | None, counts [B] i32)."""
+    def f64(lo, hi, *shape):
+        return buf[lo:hi].view(np.float64).reshape(B, *shape) if hi > lo else None
+    return dict(planes=f64(L["planes"], L["calib"], 6, 4), calib=f64(L["calib"], L["words"], CALIB_DOUBLES),
+                seq=None if L["seq"] is None else buf[L["seq"]:L["counts"]].view(np.int32),
+                counts=buf[L["counts"]:L["total"]].view(np.int32))
 
 
 class FrameStatusError(RuntimeError):
@@ -367,11 +393,11 @@ class FrameRing:
 
 
 class _PlanSlot:
-    """One frame in flight: an InferencePlan captured with the seal as its last node, its HIP stream, a pinned staging block
-    [seq, npts[B] | B x points_cap x ndim f32], a pinned record buffer and the event behind the record's copy.
-    With raw_cap the frame crops: the block is [planes[B,6,4] f64 | seq, nraw[B] | B x raw_cap x ndim f32], the clouds go
-    to plan.raw_in and the plan's first nodes cut them down to points_cap rows of plan.pts_in.  With annos the block
-    carries the calibration too, [planes | calib[B,36] f64 | seq, n[B]], and the record is layout version 2."""
+    """One frame in flight: an InferencePlan captured with the seal as its last node, its HIP stream, the pinned host side
+    of the plan's staging block (`stage_layout`: planes with raw_cap, calibration with annos, seq, counts), pinned clouds
+    [B x points_cap x ndim f32], a pinned record buffer and the event behind the record's copy.
+    With raw_cap the frame crops: the pinned clouds are [B x raw_cap x ndim f32], they go to plan.raw_in and the plan's
+    first nodes cut them down to points_cap rows of plan.pts_in.  With annos the record is layout version 2."""
 
     def __init__(self, plan, points_cap, ndim, raw_cap=None, annos=False):
         import torch
@@ -384,45 +410,35 @@ class _PlanSlot:
         self.cap, self.ndim = int(points_cap), int(ndim)
         self.raw_cap = None if raw_cap is None else int(raw_cap)
         self.annos = bool(annos)
-        self.blocked = self.raw_cap is not None or self.annos
-        nwords = 1 + B
-        if not self.blocked:
-            self.pin_words = torch.zeros(nwords, dtype=torch.int32).pin_memory()
-            self.dev_words = plan._stage_words
-        else:                       # one pinned block shaped like plan._stage_block: planes, calibration, then the words
-            self.pin_block = torch.zeros(plan._stage_block.numel(), dtype=torch.uint8).pin_memory()
-            nplane = B * 6 * 4 * 8 if self.raw_cap is not None else 0
-            ncal = B * CALIB_DOUBLES * 8 if self.annos else 0
-            if nplane:
-                self.np_planes = self.pin_block[:nplane].view(torch.float64).view(B, 6, 4).numpy()
-            if ncal:
-                self.np_calib = self.pin_block[nplane:nplane + ncal].view(torch.float64).view(B, CALIB_DOUBLES).numpy()
-            self.pin_words = self.pin_block[nplane + ncal:].view(torch.int32)
-            self.dev_words = plan._stage_block
+        L = stage_layout(B, self.raw_cap is not None, self.annos, seal=True)
+        self.pin_block = torch.zeros(L["total"], dtype=torch.uint8).pin_memory()     # the host side of plan._stage_block
+        self.np_stage = stage_views(self.pin_block.numpy(), B, L)
         self.dev_pts, rows = (plan.pts_in, self.cap) if self.raw_cap is None else (plan.raw_in, self.raw_cap)
         self.pin_pts = torch.zeros(B, rows, self.ndim, dtype=torch.float32).pin_memory()
         self.pin_rec = torch.zeros(plan.record.numel(), dtype=torch.uint8).pin_memory()
-        self.np_words, self.np_pts, self.np_rec = self.pin_words.numpy(), self.pin_pts.numpy(), self.pin_rec.numpy()
+        self.np_pts, self.np_rec = self.pin_pts.numpy(), self.pin_rec.numpy()
         self.event = torch.cuda.Event()
         self.feed = torch.cuda.Event()          # orders device-tensor clouds (produced on the caller's stream) before their copy
 
     def stage(self, seq, clouds, frustums=None, calibs=None):
         torch, plan = self.torch, self.plan
-        planes = check_frame_inputs(clouds, frustums, plan.B, self.ndim, self.cap, self.raw_cap, calibs,
-                                    self.annos)                                              # nothing is queued before this
-        if self.annos:
-            planes, self.np_calib[...] = planes
+        checked = check_frame_inputs(clouds, frustums, plan.B, self.ndim, self.cap, self.raw_cap, calibs,
+                                     self.annos)                                             # nothing is queued before this
+        view = self.np_stage
+        planes, calib = checked if self.annos else (checked, None)
         if planes is not None:
-            self.np_planes[...] = planes
+            view["planes"][...] = planes
+        if calib is not None:
+            view["calib"][...] = calib
         on_dev = [torch.is_tensor(p) and p.is_cuda for p in clouds]
         if any(on_dev):
             self.feed.record(torch.cuda.current_stream(plan.dev))
             self.stream.wait_event(self.feed)
-        self.np_words[0] = seq
+        view["seq"][0] = seq
         with torch.cuda.stream(self.stream):
             for b, pts in enumerate(clouds):
                 n = int(pts.shape[0])
-                self.np_words[1 + b] = n
+                view["counts"][b] = n
                 if n == 0:
                     continue
                 if on_dev[b]:
@@ -432,7 +448,7 @@ class _PlanSlot:
                 else:
                     self.np_pts[b, :n] = pts.numpy() if torch.is_tensor(pts) else pts
                     self.dev_pts[b][:n].copy_(self.pin_pts[b, :n], non_blocking=True)
-            self.dev_words.copy_(self.pin_block if self.blocked else self.pin_words, non_blocking=True)
+            plan._stage_block.copy_(self.pin_block, non_blocking=True)
 
     def launch(self):
         torch = self.torch

@@ -79,6 +79,70 @@ def test_record_layout_rejects_impossible_shapes():
             record_layout(B, capD)
 
 
+# ---- staging block arithmetic -----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("B", [1, 2, 3, 8])
+@pytest.mark.parametrize("raw", [False, True])
+@pytest.mark.parametrize("annos", [False, True])
+@pytest.mark.parametrize("seal", [False, True])
+def test_stage_layout_arithmetic(B, raw, annos, seal):
+    from sassd.stream import stage_layout, CALIB_DOUBLES
+    assert CALIB_DOUBLES == 36
+    L = stage_layout(B, raw, annos, seal)
+    assert set(L) == {"planes", "calib", "words", "seq", "counts", "total"}
+    assert L["planes"] == 0
+    assert L["calib"] == 192 * B * raw
+    assert L["words"] == L["calib"] + 288 * B * annos
+    assert L["seq"] == (L["words"] if seal else None)
+    assert L["counts"] == L["words"] + 4 * seal
+    assert L["total"] == 192 * B * raw + 288 * B * annos + 4 * (B + seal)
+    assert L["planes"] % 8 == 0 and L["calib"] % 8 == 0 and L["words"] % 4 == 0
+    assert stage_layout(B, raw=raw, annos=annos, seal=seal) == L
+
+
+def test_stage_layout_rejects_an_empty_batch():
+    from sassd.stream import stage_layout
+    for B in (0, -1):
+        with pytest.raises(ValueError):
+            stage_layout(B, True, True, True)
+
+
+def test_stage_views_alias_the_buffer_at_the_layouts_offsets():
+    from sassd.stream import stage_layout, stage_views
+    B, guard = 3, 64
+    L = stage_layout(B, True, True, True)
+    whole = np.full(L["total"] + 2 * guard, 0xA5, np.uint8)
+    buf = whole[guard:guard + L["total"]]
+    V = stage_views(buf, B, L)
+    assert set(V) == {"planes", "calib", "seq", "counts"}
+    assert V["planes"].shape == (B, 6, 4) and V["planes"].dtype == np.float64
+    assert V["calib"].shape == (B, 36) and V["calib"].dtype == np.float64
+    assert V["seq"].shape == (1,) and V["seq"].dtype == np.int32
+    assert V["counts"].shape == (B,) and V["counts"].dtype == np.int32
+    for v in V.values():
+        assert np.shares_memory(v, buf) and np.shares_memory(v, whole)
+    planes = 1000.5 + np.arange(B * 24, dtype=np.float64).reshape(B, 6, 4)
+    calib = -7.25 - np.arange(B * 36, dtype=np.float64).reshape(B, 36)
+    counts = np.asarray([70001, 70002, 70003], np.int32)
+    V["planes"][...], V["calib"][...], V["seq"][0], V["counts"][...] = planes, calib, 0x12345678, counts
+    raw = whole.tobytes()
+    assert np.array_equal(np.frombuffer(raw, np.float64, B * 24, offset=guard + L["planes"]), planes.ravel())
+    assert np.array_equal(np.frombuffer(raw, np.float64, B * 36, offset=guard + L["calib"]), calib.ravel())
+    assert np.frombuffer(raw, np.int32, 1, offset=guard + L["seq"])[0] == 0x12345678
+    assert np.array_equal(np.frombuffer(raw, np.int32, B, offset=guard + L["counts"]), counts)
+    assert (whole[:guard] == 0xA5).all() and (whole[guard + L["total"]:] == 0xA5).all()      # nothing outside the block
+    assert not (buf == 0xA5).all()
+    # the four parts tile the block: every byte of it belongs to exactly one view
+    assert sum(v.nbytes for v in V.values()) == L["total"]
+    # lesser forms: the absent parts are None, the present ones keep their shapes
+    for raw_, annos, seal in ((False, False, False), (False, False, True), (True, False, False), (False, True, True)):
+        Lf = stage_layout(B, raw_, annos, seal)
+        Vf = stage_views(np.zeros(Lf["total"] + 8, np.uint8), B, Lf)         # a longer buffer is fine
+        assert (Vf["planes"] is not None) == raw_ and (Vf["calib"] is not None) == annos and (Vf["seq"] is not None) == seal
+        assert Vf["counts"].shape == (B,) and Vf["counts"].dtype == np.int32
+        assert raw_ is False or Vf["planes"].shape == (B, 6, 4)
+        assert annos is False or Vf["calib"].shape == (B, 36)
+
+
 # ---- the decoder on hand-built records --------------------------------------------------------------------------------------
 def build_record(B, capD, seq, counts, status=0, magic=None, seed=0):
     """A record as the seal kernel writes it (numpy model of the contract) + the detections it holds."""

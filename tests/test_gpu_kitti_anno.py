@@ -9,9 +9,10 @@ import torch
 import sassd  # noqa: F401
 from sassd import kernels as K, kitti_common as kc
 from sassd.pipeline import InferencePlan
-from sassd.stream import record_layout
+from sassd.stream import frustum_of, record_layout, stage_layout
 import kitti_anno_cases as KA
 import test_gpu_frame_stream as TS
+import test_gpu_frame_stream_crop as TC
 
 pytestmark = pytest.mark.gpu
 
@@ -159,6 +160,45 @@ def test_annos_frame_holds_kernel_nodes_only(dev):
         assert got[KERNEL] == base[KERNEL] + 2                          # the seal and the annotation kernel
         t = fs.submit([_frames()[0]], calibs=[CAL])                     # the stream still works after the inspection
         assert _check_frame(fs.collect(t), {}) >= 0
+
+
+def test_full_staging_block_at_batch_2(dev):
+    """raw_cap + annos at batch 2: every part of the staging block present, per-sample offsets in play.  Each sample has its
+    own sweep and image shape, hence its own planes and calibration block: a swapped or shifted sample index shows."""
+    shapes = [(375, 1242), (370, 1224)]
+    views = [dict(calib=KA.calibration(), img_shape=s) for s in shapes]
+    raws = [TC.raw_sweep(b)[0] for b in range(2)]
+    reds = [TC.reduce_on_host(raw, frustum_of(v["calib"], v["img_shape"])) for raw, v in zip(raws, views)]
+    assert [len(r) for r in reds] == [14986, 14516] and max(len(r) for r in raws) <= TC.RAW_CAP
+    sd, w, _ = TS._workload(dev)
+    assert max(len(r) for r in reds) <= w["points_cap"]
+
+    def aliases(plan, L, **parts):
+        assert plan._stage_block.dtype == torch.uint8 and plan._stage_block.numel() == L["total"]
+        for name, tensor in parts.items():
+            assert tensor.data_ptr() == plan._stage_block.data_ptr() + L[name], name
+
+    with TS._stream(sd, w, dev, 1, B=2) as ref:
+        want = ref.collect(ref.submit(reds))
+        p = ref.plans[0]
+        aliases(p, stage_layout(2, seal=True), seq=p._seq, counts=p.npts)
+    n_det = sum(len(s[0]) for s in want if s[0] is not None)
+    print("batch 2, kept points %s: %d detections" % ([len(r) for r in reds], n_det))
+    assert n_det >= 1, "the two sweeps detect nothing: the comparison would be empty"
+    with TS._stream(sd, w, dev, 1, B=2, raw_cap=TC.RAW_CAP, annos=True) as fs:
+        p = fs.plans[0]
+        assert p.raw_cap == TC.RAW_CAP and p.crop_planes.shape == (2, 6, 4) and p.calib.shape == (2, 36)
+        aliases(p, stage_layout(2, True, True, True), planes=p.crop_planes, calib=p.calib, seq=p._seq, counts=p.nraw)
+        got = fs.collect(fs.submit(raws, views))                        # the frustum dicts serve as calibs too
+        assert int(p.status.item()) == 0
+    TS._same_dets([s[:3] for s in got], want, "raw + annos at batch 2")
+    maxima = {}
+    for (boxes, scores, labels, cam), shape in zip(got, shapes):
+        if boxes is None:
+            assert cam is None
+            continue
+        KA.compare(cam, boxes, scores, labels, img_shape=shape, maxima=maxima)
+    print("maxima", maxima)
 
 
 def test_single_test_device_annos_equals_the_host_path(dev, tmp_path):
