@@ -599,6 +599,33 @@ int sassd_pswarp_sample(const float *feat, int batch, int H, int W, const float 
                         const int32_t *counts, int capK, float grid_off_x, float grid_off_y,
                         float spatial_scale, float *logits, void *stream);
 
+/* The part-sensitive head at the pixels sassd_pswarp_sample reads, and nowhere else.
+ *
+ * sassd_ps_pixel_list: the set of pixels sassd_pswarp_sample(guided, counts, capK, offsets, scale) would read from a
+ *   [B,28,H,W] map -- for every box < min(counts[b], capK) and grid point k < 28 the in-map ones of its four bilinear
+ *   neighbours, by the same device function as the sampler (bit-equal geometry).  `list` is int32, 16-byte aligned,
+ *   sassd_ps_pixel_list_ints(B, H, W) ints (0: unsupported shape), laid out as
+ *     [0, B)                       the number of listed pixels per sample,
+ *     [HEAD, HEAD + B H W)         HEAD = B rounded up to 4: per sample H W slots, the first count[b] of them the listed
+ *                                  linear pixels y W + x in ascending order (the others keep stale values),
+ *     behind, 4-int aligned        B x (H W rounded up to 16) flag bytes: 1 at a listed pixel, 0 elsewhere.
+ *   Deterministic; three kernel launches (fill, mark, compact), no memset node, no host read; every call clears the flags
+ *   itself, so nothing of an earlier call survives in counts, in the listed prefix or in the flags.
+ * sassd_ps_head_sampled: y[b, :, p] = conv1x1(relu?(conv3x3(x) * scale0 + shift0)) * scale1 + shift1 at every listed pixel p
+ *   of `list` (the layout above; only counts and lists are read; entries outside [0, H W) are skipped), all other pixels of
+ *   y [B,parts,H,W] untouched.  x [B,Cin,H,W] fp32, w_packed from sassd_conv2d_pack_weight(ksize 3), wT the transposed
+ *   [parts][CO] image of sassd_conv1x1_narrow_fwd; scale / shift pointers may be NULL (1 / 0).  The stored values are
+ *   BIT-IDENTICAL to sassd_conv2d_fwd(ksize 3) followed by sassd_conv1x1_narrow_fwd at those pixels (both summation orders
+ *   are repeated: csrc/conv2d.hip).  Needs Cin % 32 == 0 and parts <= 32 (sassd_ps_head_sampled_supported), list 16-byte
+ *   aligned.  One launch whose grid covers the worst case, every pixel listed; no fall-back to the dense kernels. */
+size_t sassd_ps_pixel_list_ints(int batch, int H, int W);
+int sassd_ps_pixel_list(const float *guided, const int32_t *counts, int capK, int batch, int H, int W,
+                        float grid_off_x, float grid_off_y, float spatial_scale, int32_t *list, void *stream);
+int sassd_ps_head_sampled_supported(int Cin, int parts);
+int sassd_ps_head_sampled(const float *x, const float *w_packed, const float *scale0, const float *shift0, int relu0,
+                          const float *wT, const float *scale1, const float *shift1, int relu1, const int32_t *list,
+                          float *y, int batch, int Cin, int parts, int H, int W, void *stream);
+
 /* backward of sassd_pswarp_sample (training, PSWarpHead.loss): dlogits [B,capK] -> ACCUMULATES into dfeat [B,28,H,W]
  * (caller zeroes; float atomics) and writes dguided [B,capK,7] (d/d x,y,w,l,r; z,h columns zero; may be NULL) --
  * torch.nn.functional.grid_sample differentiates w.r.t. both input and grid (ssd_rotate_head.py:400-414). */

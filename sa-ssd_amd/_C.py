@@ -93,6 +93,11 @@ _SIGS = {
     "sassd_decode_filter": (_I, [_P, _P, _P, _SZ, _I, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _I, _P, _P, _SZ, _P]),
     "sassd_pswarp_sample": (_I, [_P, _I, _I, _I, _P, _P, _I, _F, _F, _F, _P, _P]),
     "sassd_pswarp_sample_bwd": (_I, [_P, _I, _I, _I, _P, _P, _I, _F, _F, _F, _P, _P, _P, _P]),
+    # the part-sensitive head at the sampled pixels (include/sassd.h, behind sassd_pswarp_sample)
+    "sassd_ps_pixel_list_ints": (_SZ, [_I, _I, _I]),
+    "sassd_ps_pixel_list": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _F, _P, _P]),
+    "sassd_ps_head_sampled_supported": (_I, [_I, _I]),
+    "sassd_ps_head_sampled": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     "sassd_rescore_nms_workspace_bytes": (_SZ, [_I, _I]),
     "sassd_rescore_nms": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _P, _I, _P, _P, _SZ, _P]),
     # frame record (include/sassd.h "Frame record"; sassd.stream)

@@ -560,3 +560,173 @@ extern "C" int sassd_conv1x1_narrow_fwd(const float *x, const float *wT, const f
 #undef SASSD_NARROW
     return sassd_launch_status();
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// The part-sensitive head at LISTED pixels only (sassd_ps_head_sampled): the 3x3 Cin -> parts conv (folded BatchNorm, ReLU)
+// and the 1x1 parts -> parts conv behind it, computed for the pixels of a list (heads.hip, sassd_ps_pixel_list: the pixels
+// PSWarp samples, a quarter of the map or less) and stored into the dense [B, parts, H, W] map at those pixels.  Every value
+// is BIT-IDENTICAL to what conv2d_kernel<1, 9, *> followed by conv1x1_narrow_kernel stores there, because both summation
+// orders are repeated exactly:
+//   3x3: the narrow form above -- wave w of four owns channels 8 ch + 2 w, 8 ch + 2 w + 1 of every chunk ch, one
+//        v_mfma_f32_32x32x2_f32 per (chunk, tap) in chunk -> tap order (the same instruction on the same operands: weight
+//        [kc][cout] as A, 32 pixels as B, zero for a tap outside the image, as the zero halo of the staged patch), the four
+//        partial sums added in wave order, then v * scale + shift and the ReLU in the epilogue's own words;
+//   1x1: wave w's share is channels [w q, (w + 1) q), q = ceil(parts / 4): an fmaf chain per share in channel order from 0,
+//        (p0 + p1) + (p2 + p3), then s * scale + shift.
+// A workgroup takes 32 listed pixels (one MFMA pixel tile).  There is no LDS patch to stage: each lane gathers its pixel's
+// taps from the NCHW map into a ring of four chunk buffers in registers, three chunks (27 MFMAs, ~1700 cycles) ahead of the
+// MFMAs that consume them (hence Cin % 32 == 0); at ~110 registers several workgroups share a CU and hide the rest.  The launch grid covers the worst case (every pixel listed);
+// workgroups beyond the sample's count leave at once.
+// ------------------------------------------------------------------------------------------------------------------
+namespace {
+struct PsSampledParams {
+    const float *x, *wp, *scale0, *shift0, *wT, *scale1, *shift1;
+    const int32_t *counts, *pix;      // counts [B]; pix [B][HW], the first counts[b] entries of sample b are listed pixels
+    float *y;
+    int Cin, parts, CO, H, W, HW, relu0, relu1;
+};
+
+constexpr int kPsRing = 4;            // chunk buffers in the gather ring (Cin is a multiple of 8 x this)
+
+__global__ void __launch_bounds__(256) ps_sampled_kernel(PsSampledParams P)
+{
+    constexpr int KC = 8, BMC = 32;
+    __shared__ float red[4][16][64];
+    __shared__ float hbuf[32][33];
+    const int b = blockIdx.y;
+    const int n = min(max(P.counts[b], 0), P.HW);
+    const int i0 = blockIdx.x * 32;
+    if (i0 >= n) return;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int32_t *pl = P.pix + (size_t)b * P.HW;
+
+    // this lane's pixel (lanes 32..63 mirror 0..31 on the next channel) and its nine taps: an offset from the wave's
+    // channel pair, and a mask bit -- a tap outside the image is loaded from the pixel itself and replaced by zero in
+    // front of its MFMA (not behind its load: the select would wait for the gather it is meant to run ahead of)
+    int off[9];
+    unsigned vmask = 0;
+    {
+        const int i = i0 + (lane & 31);
+        int p = i < n ? pl[i] : -1;
+        const bool ok = p >= 0 && p < P.HW;
+        p = ok ? p : 0;
+        const int py = p / P.W, px = p - py * P.W;
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int yy = py + tap / 3 - 1, xx = px + tap % 3 - 1;
+            const bool in = ok && yy >= 0 && yy < P.H && xx >= 0 && xx < P.W;
+            off[tap] = (in ? yy * P.W + xx : p) + (lane >> 5) * P.HW;
+            vmask |= in ? 1u << tap : 0u;
+        }
+    }
+    // buffer loads: one 32-bit byte offset per lane and tap for the whole K loop (9 registers), the chunk's and the wave's
+    // share of the address in the scalar offset -- 64-bit lane addresses per (chunk, tap) cost more registers than the operands.  Every offset lies inside its buffer: channel 2 wave + (lane >> 5), weight row [kc][cout = lane & 31].
+    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void *)(P.x + (size_t)b * P.Cin * P.HW), 0,
+                                                                         P.Cin * P.HW * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void *)P.wp, 0, P.Cin * 9 * BMC * 4, 0x00020000);
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) off[tap] *= 4;
+    const int xso = 2 * wave * P.HW * 4, wso = 2 * wave * BMC * 4;
+    const int nchunk = P.Cin / KC;                                       // a multiple of kPsRing
+
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+
+    // a ring of kPsRing chunk buffers (9 weight + 9 pixel operands each), three chunks = 54 loads in flight behind the chunk
+    // the MFMAs consume: s_waitcnt counts at most 63 outstanding loads, so a deeper ring would wait for all of them
+    float av[kPsRing][9], bv[kPsRing][9];
+    auto gather = [&](int ch, float (&a)[9], float (&v)[9]) {
+        const int xo = xso + ch * KC * P.HW * 4, wo = wso + ch * 9 * KC * BMC * 4;
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            v[tap] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, off[tap], xo, 0));
+            a[tap] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(wr, lane * 4 + tap * KC * BMC * 4, wo, 0));
+        }
+    };
+    auto mma = [&](const float (&a)[9], const float (&v)[9]) {
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[tap], ((vmask >> tap) & 1u) ? v[tap] : 0.f, acc, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+#pragma unroll
+    for (int u = 0; u < kPsRing - 1; ++u) gather(u, av[u], bv[u]);
+    int ch = 0;
+    for (; ch < nchunk - kPsRing; ch += kPsRing) {
+#pragma unroll
+        for (int u = 0; u < kPsRing; ++u) {
+            gather(ch + u + kPsRing - 1, av[(u + kPsRing - 1) % kPsRing], bv[(u + kPsRing - 1) % kPsRing]);
+            mma(av[u], bv[u]);
+        }
+    }
+    gather(ch + kPsRing - 1, av[kPsRing - 1], bv[kPsRing - 1]);          // the last group: one chunk left to fetch
+#pragma unroll
+    for (int u = 0; u < kPsRing; ++u) mma(av[u], bv[u]);
+
+    // ---- the narrow form's cross-wave K reduction and epilogue: D[row = cout][col = pixel] --------------------------------
+#pragma unroll
+    for (int r = 0; r < 16; ++r) red[wave][r][lane] = acc[r];
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int r = wave + 4 * q;
+        const int co = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        float v = red[0][r][lane] + red[1][r][lane] + red[2][r][lane] + red[3][r][lane];
+        if (co < P.parts) {
+            v = v * (P.scale0 ? P.scale0[co] : 1.f) + (P.shift0 ? P.shift0[co] : 0.f);
+            if (P.relu0) v = fmaxf(v, 0.f);
+        }
+        hbuf[co][lane & 31] = v;
+    }
+    __syncthreads();
+
+    // ---- the 1x1 behind it: conv1x1_narrow_kernel's four channel shares, chains and pairing ------------------------------
+    const int pi = tid & 31;
+    const int i = i0 + pi;
+    const int p = i < n ? pl[i] : -1;
+    const bool ok = p >= 0 && p < P.HW;
+    const int cq = (P.parts + 3) / 4;
+    for (int j = tid >> 5; j < P.parts; j += 8) {
+        float part[4];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            float a = 0.f;
+            const int c1 = min(w * cq + cq, P.parts);
+            for (int c = w * cq; c < c1; ++c) a = fmaf(hbuf[c][pi], P.wT[(size_t)c * P.CO + j], a);
+            part[w] = a;
+        }
+        float s = (part[0] + part[1]) + (part[2] + part[3]);
+        s = s * (P.scale1 ? P.scale1[j] : 1.f) + (P.shift1 ? P.shift1[j] : 0.f);
+        if (P.relu1) s = fmaxf(s, 0.f);
+        if (ok) P.y[((size_t)b * P.parts + j) * P.HW + p] = s;
+    }
+}
+}  // namespace
+
+extern "C" int sassd_ps_head_sampled_supported(int Cin, int parts)
+{
+    return Cin >= 32 && Cin % 32 == 0 && parts >= 1 && parts <= 32 ? 1 : 0;
+}
+
+extern "C" int sassd_ps_head_sampled(const float *x, const float *w_packed, const float *scale0, const float *shift0,
+                                     int relu0, const float *wT, const float *scale1, const float *shift1, int relu1,
+                                     const int32_t *list, float *y, int batch, int Cin, int parts, int H, int W,
+                                     void *stream_)
+{
+    if (!x || !w_packed || !wT || !list || !y || batch < 1 || H < 1 || W < 2) return SASSD_EINVAL;
+    if (!sassd_ps_head_sampled_supported(Cin, parts) || ((uintptr_t)list & 15)) return SASSD_EINVAL;
+    // (32-bit byte offsets into one sample's map and into the weight image)
+    if ((size_t)batch * H * W > ((size_t)1 << 30) || (size_t)Cin * H * W >= ((size_t)1 << 29)) return SASSD_EINVAL;
+    PsSampledParams P;
+    P.x = x; P.wp = w_packed; P.scale0 = scale0; P.shift0 = shift0; P.wT = wT; P.scale1 = scale1; P.shift1 = shift1;
+    P.counts = list; P.pix = list + (batch + 3) / 4 * 4;      // the layout of sassd_ps_pixel_list
+    P.y = y;
+    P.Cin = Cin; P.parts = parts; P.CO = sassd_conv1x1_narrow_pad(parts); P.H = H; P.W = W; P.HW = H * W;
+    P.relu0 = relu0; P.relu1 = relu1;
+    hipLaunchKernelGGL(ps_sampled_kernel, dim3((unsigned)cdiv(P.HW, 32), (unsigned)batch), dim3(256), 0,
+                       (hipStream_t)stream_, P);
+    return sassd_launch_status();
+}

@@ -138,6 +138,44 @@ struct WarpParams {
     float lin4[4], lin7[7];
 };
 
+// The tap geometry of PSWarp, stated ONCE: grid point k = (ix, iy) of box `box` -> its four bilinear neighbour pixels, their
+// weights and which of them lie inside the map.  pswarp_kernel, its two backward kernels and ps_mark_kernel (the list of
+// pixels the sampled part-sensitive head computes) all call this, so they agree on every tap bit for bit.
+struct PsTap {
+    float ct, st, xx, yy;                  // cos / sin of the box angle, the grid point in the box frame
+    int x0, y0, x1, y1;
+    float wx0, wx1, wy0, wy1;
+    bool inr;                              // the sample lies inside (-1, W) x (-1, H): else every tap is padding
+    bool xin0, xin1, yin0, yin1;
+};
+
+__device__ __forceinline__ PsTap ps_tap(const WarpParams &P, int b, int box, int ix, int iy)
+{
+    PsTap t;
+    const float *g = P.guided + ((size_t)b * P.capK + box) * 7;
+    const float xg = g[0], yg = g[1], wg = g[3], lg = g[4], rg = g[6];
+    const float ct = cosf(rg), st = sinf(rg);
+    const float xx = P.lin4[ix] * wg, yy = P.lin7[iy] * lg;
+    const float x = xx * ct + yy * st + xg;
+    const float y = yy * ct - xx * st + yg;
+    const float u = (x + P.offx) * P.scale, v = (y + P.offy) * P.scale;
+    // normalise exactly like bilinear_interpolate_torch_gridsample, then grid_sample(align_corners=True)
+    const float gx = u / (float)(P.W - 1) * 2.f - 1.f, gy = v / (float)(P.H - 1) * 2.f - 1.f;
+    float fx = (gx + 1.f) / 2.f * (float)(P.W - 1), fy = (gy + 1.f) / 2.f * (float)(P.H - 1);
+    t.inr = fx > -1.f && fx < (float)P.W && fy > -1.f && fy < (float)P.H;
+    // keep the float -> int conversion and the +1 in range (int overflow is UB and hipcc exploits it in the
+    // bounds tests); samples outside [-1, size] contribute zero either way (zero padding), NaN -> outside
+    fx = fminf(fmaxf(fx, -2.f), (float)P.W + 1.f);
+    fy = fminf(fmaxf(fy, -2.f), (float)P.H + 1.f);
+    const float x0f = floorf(fx), y0f = floorf(fy);
+    t.x0 = (int)x0f; t.y0 = (int)y0f; t.x1 = t.x0 + 1; t.y1 = t.y0 + 1;
+    t.wx1 = fx - x0f; t.wx0 = (x0f + 1.f) - fx; t.wy1 = fy - y0f; t.wy0 = (y0f + 1.f) - fy;
+    t.xin0 = t.x0 >= 0 && t.x0 < P.W; t.xin1 = t.x1 >= 0 && t.x1 < P.W;
+    t.yin0 = t.y0 >= 0 && t.y0 < P.H; t.yin1 = t.y1 >= 0 && t.y1 < P.H;
+    t.ct = ct; t.st = st; t.xx = xx; t.yy = yy;
+    return t;
+}
+
 __global__ void __launch_bounds__(256) pswarp_kernel(WarpParams P)
 {
     const int b = blockIdx.y;
@@ -146,27 +184,12 @@ __global__ void __launch_bounds__(256) pswarp_kernel(WarpParams P)
     const int k = threadIdx.x & 31;
     float val = 0.f;
     if (box < K && k < 28) {
-        const float *g = P.guided + ((size_t)b * P.capK + box) * 7;
-        const float xg = g[0], yg = g[1], wg = g[3], lg = g[4], rg = g[6];
-        const float ct = cosf(rg), st = sinf(rg);
         const int ix = k / 7, iy = k - ix * 7;
-        const float xx = P.lin4[ix] * wg, yy = P.lin7[iy] * lg;
-        const float x = xx * ct + yy * st + xg;
-        const float y = yy * ct - xx * st + yg;
-        const float u = (x + P.offx) * P.scale, v = (y + P.offy) * P.scale;
-        // normalise exactly like bilinear_interpolate_torch_gridsample, then grid_sample(align_corners=True)
-        const float gx = u / (float)(P.W - 1) * 2.f - 1.f, gy = v / (float)(P.H - 1) * 2.f - 1.f;
-        float fx = (gx + 1.f) / 2.f * (float)(P.W - 1), fy = (gy + 1.f) / 2.f * (float)(P.H - 1);
-        // keep the float -> int conversion and the +1 in range (int overflow is UB and hipcc exploits it in the
-        // bounds tests); samples outside [-1, size] contribute zero either way (zero padding), NaN -> outside
-        fx = fminf(fmaxf(fx, -2.f), (float)P.W + 1.f);
-        fy = fminf(fmaxf(fy, -2.f), (float)P.H + 1.f);
-        const float x0f = floorf(fx), y0f = floorf(fy);
-        const int x0 = (int)x0f, y0 = (int)y0f, x1 = x0 + 1, y1 = y0 + 1;
-        const float wx1 = fx - x0f, wx0 = (x0f + 1.f) - fx, wy1 = fy - y0f, wy0 = (y0f + 1.f) - fy;
+        const PsTap t = ps_tap(P, b, box, ix, iy);
+        const int x0 = t.x0, y0 = t.y0, x1 = t.x1, y1 = t.y1;
+        const float wx0 = t.wx0, wx1 = t.wx1, wy0 = t.wy0, wy1 = t.wy1;
+        const bool xin0 = t.xin0, xin1 = t.xin1, yin0 = t.yin0, yin1 = t.yin1;
         const float *im = P.feat + ((size_t)b * 28 + k) * P.H * P.W;
-        const bool xin0 = x0 >= 0 && x0 < P.W, xin1 = x1 >= 0 && x1 < P.W;
-        const bool yin0 = y0 >= 0 && y0 < P.H, yin1 = y1 >= 0 && y1 < P.H;
         if (yin0 && xin0) val += im[(size_t)y0 * P.W + x0] * (wx0 * wy0);
         if (yin0 && xin1) val += im[(size_t)y0 * P.W + x1] * (wx1 * wy0);
         if (yin1 && xin0) val += im[(size_t)y1 * P.W + x0] * (wx0 * wy1);
@@ -175,6 +198,59 @@ __global__ void __launch_bounds__(256) pswarp_kernel(WarpParams P)
 #pragma unroll
     for (int o = 16; o >= 1; o >>= 1) val += __shfl_xor(val, o, 32);
     if (box < K && k == 0) P.logits[(size_t)b * P.capK + box] = val / 28.f;
+}
+
+// ---- the pixels pswarp_kernel reads (sassd_ps_pixel_list) ------------------------------------------------------------------
+// pswarp_kernel reads the part-sensitive map at four neighbour pixels per (box, grid point) and nowhere else, so the
+// part-sensitive head needs computing at those pixels only (conv2d.hip, ps_sampled_kernel).  Two launches behind one fill,
+// the pattern of the Winograd tile map (w4_mark_kernel / w4_compact_kernel):
+//   1. ps_mark_kernel     pswarp_kernel's launch geometry and ps_tap: a byte flag per in-map neighbour (benign same-value
+//                         stores, no atomics)
+//   2. ps_compact_kernel  ordered compaction per sample, one pixel per thread: a workgroup's base = the flags in front of its
+//                         1024 pixels (summed again by every workgroup: H W bytes at most, no grid barrier, no atomics)
+// The list of sample b comes out in ascending (row-major) pixel order, so neighbours in a row stay neighbours in the list.
+constexpr int kPsBlock = 1024;
+inline size_t ps_list_head(int B) { return align_up((size_t)B, 4); }                                   // ints: counts[B]
+inline size_t ps_flag_stride(size_t HW) { return align_up(HW, 16); }                                   // bytes per sample
+inline size_t ps_flag_off(int B, size_t HW) { return ps_list_head(B) + align_up((size_t)B * HW, 4); }  // ints
+
+__global__ void __launch_bounds__(256) ps_mark_kernel(WarpParams P, unsigned char *__restrict__ flags, int fstride)
+{
+    const int b = blockIdx.y;
+    const int K = min(P.counts[b], P.capK);
+    const int box = blockIdx.x * 8 + (threadIdx.x >> 5);
+    const int k = threadIdx.x & 31;
+    if (box < K && k < 28) {
+        const int ix = k / 7, iy = k - ix * 7;
+        const PsTap t = ps_tap(P, b, box, ix, iy);
+        unsigned char *f = flags + (size_t)b * fstride;
+        if (t.yin0 && t.xin0) f[(size_t)t.y0 * P.W + t.x0] = 1;
+        if (t.yin0 && t.xin1) f[(size_t)t.y0 * P.W + t.x1] = 1;
+        if (t.yin1 && t.xin0) f[(size_t)t.y1 * P.W + t.x0] = 1;
+        if (t.yin1 && t.xin1) f[(size_t)t.y1 * P.W + t.x1] = 1;
+    }
+}
+
+__global__ void __launch_bounds__(kPsBlock) ps_compact_kernel(const unsigned char *__restrict__ flags, int fstride, int HW,
+                                                              int32_t *__restrict__ counts, int32_t *__restrict__ pix)
+{
+    __shared__ int wsum[17];
+    const int b = blockIdx.y;
+    const unsigned char *f = flags + (size_t)b * fstride;
+    const int t0 = blockIdx.x * kPsBlock;                // (a multiple of 16: whole 16-byte words in front of this workgroup)
+    int before = 0;
+    for (int i = threadIdx.x; i < t0 / 16; i += kPsBlock) {
+        const uint4 w = ((const uint4 *)f)[i];           // flag bytes are 0 or 1
+        before += __popc(w.x) + __popc(w.y) + __popc(w.z) + __popc(w.w);
+    }
+    int base;
+    block_exclusive_scan(before, wsum, &base);
+    const int t = t0 + threadIdx.x;
+    const int on = t < HW ? (int)f[t] : 0;
+    int total;
+    const int j = base + block_exclusive_scan(on, wsum, &total);
+    if (on) pix[(size_t)b * HW + j] = t;
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) counts[b] = base + total;
 }
 
 // backward of pswarp_kernel (training): d logits -> d feat (atomicAdd into [B,28,H,W]) and d guided [B,capK,7]
@@ -190,28 +266,17 @@ __global__ void __launch_bounds__(256) pswarp_bwd_kernel(WarpParams P, const flo
     const int k = threadIdx.x & 31;
     float gxg = 0.f, gyg = 0.f, gw = 0.f, gl = 0.f, gr = 0.f;
     if (box < K && k < 28) {
-        const float *g = P.guided + ((size_t)b * P.capK + box) * 7;
-        const float xg = g[0], yg = g[1], wg = g[3], lg = g[4], rg = g[6];
-        const float ct = cosf(rg), st = sinf(rg);
         const int ix = k / 7, iy = k - ix * 7;
-        const float xx = P.lin4[ix] * wg, yy = P.lin7[iy] * lg;
-        const float x = xx * ct + yy * st + xg;
-        const float y = yy * ct - xx * st + yg;
-        const float u = (x + P.offx) * P.scale, v = (y + P.offy) * P.scale;
-        const float gx = u / (float)(P.W - 1) * 2.f - 1.f, gy = v / (float)(P.H - 1) * 2.f - 1.f;
-        float fx = (gx + 1.f) / 2.f * (float)(P.W - 1), fy = (gy + 1.f) / 2.f * (float)(P.H - 1);
-        const bool inr = fx > -1.f && fx < (float)P.W && fy > -1.f && fy < (float)P.H;   // else: all taps padded
-        fx = fminf(fmaxf(fx, -2.f), (float)P.W + 1.f);
-        fy = fminf(fmaxf(fy, -2.f), (float)P.H + 1.f);
-        const float x0f = floorf(fx), y0f = floorf(fy);
-        const int x0 = (int)x0f, y0 = (int)y0f, x1 = x0 + 1, y1 = y0 + 1;
-        const float wx1 = fx - x0f, wx0 = (x0f + 1.f) - fx, wy1 = fy - y0f, wy0 = (y0f + 1.f) - fy;
+        const PsTap t = ps_tap(P, b, box, ix, iy);
+        const float ct = t.ct, st = t.st, xx = t.xx, yy = t.yy;
+        const bool inr = t.inr;
+        const int x0 = t.x0, y0 = t.y0, x1 = t.x1, y1 = t.y1;
+        const float wx0 = t.wx0, wx1 = t.wx1, wy0 = t.wy0, wy1 = t.wy1;
+        const bool xin0 = t.xin0, xin1 = t.xin1, yin0 = t.yin0, yin1 = t.yin1;
         const float go = dlogits[(size_t)b * P.capK + box] / 28.f;
         const size_t plane = ((size_t)b * 28 + k) * P.H * P.W;
         const float *im = P.feat + plane;
         float *di = dfeat + plane;
-        const bool xin0 = x0 >= 0 && x0 < P.W, xin1 = x1 >= 0 && x1 < P.W;
-        const bool yin0 = y0 >= 0 && y0 < P.H, yin1 = y1 >= 0 && y1 < P.H;
         float v00 = 0.f, v01 = 0.f, v10 = 0.f, v11 = 0.f;
         if (inr) {
             if (yin0 && xin0) { v00 = im[(size_t)y0 * P.W + x0]; if (kDfeat) atomicAdd(&di[(size_t)y0 * P.W + x0], go * wx0 * wy0); }
@@ -265,25 +330,12 @@ __global__ void __launch_bounds__(256) pswarp_dfeat_det_kernel(WarpParams P, con
             const int box = c0 + i;
             unsigned long long kk[4] = {~0ull, ~0ull, ~0ull, ~0ull};
             float vv[4] = {0.f, 0.f, 0.f, 0.f};
-            // ---- the tap geometry of pswarp_bwd_kernel, statement for statement (same rounding) ----
-            const float *g = P.guided + ((size_t)b * P.capK + box) * 7;
-            const float xg = g[0], yg = g[1], wg = g[3], lg = g[4], rg = g[6];
-            const float ct = cosf(rg), st = sinf(rg);
-            const float xx = P.lin4[ix] * wg, yy = P.lin7[iy] * lg;
-            const float x = xx * ct + yy * st + xg;
-            const float y = yy * ct - xx * st + yg;
-            const float u = (x + P.offx) * P.scale, v = (y + P.offy) * P.scale;
-            const float gx = u / (float)(P.W - 1) * 2.f - 1.f, gy = v / (float)(P.H - 1) * 2.f - 1.f;
-            float fx = (gx + 1.f) / 2.f * (float)(P.W - 1), fy = (gy + 1.f) / 2.f * (float)(P.H - 1);
-            const bool inr = fx > -1.f && fx < (float)P.W && fy > -1.f && fy < (float)P.H;
-            fx = fminf(fmaxf(fx, -2.f), (float)P.W + 1.f);
-            fy = fminf(fmaxf(fy, -2.f), (float)P.H + 1.f);
-            const float x0f = floorf(fx), y0f = floorf(fy);
-            const int x0 = (int)x0f, y0 = (int)y0f, x1 = x0 + 1, y1 = y0 + 1;
-            const float wx1 = fx - x0f, wx0 = (x0f + 1.f) - fx, wy1 = fy - y0f, wy0 = (y0f + 1.f) - fy;
+            const PsTap t = ps_tap(P, b, box, ix, iy);                     // the tap geometry of pswarp_bwd_kernel
+            const bool inr = t.inr;
+            const int x0 = t.x0, y0 = t.y0, x1 = t.x1, y1 = t.y1;
+            const float wx0 = t.wx0, wx1 = t.wx1, wy0 = t.wy0, wy1 = t.wy1;
+            const bool xin0 = t.xin0, xin1 = t.xin1, yin0 = t.yin0, yin1 = t.yin1;
             const float go = dlogits[(size_t)b * P.capK + box] / 28.f;
-            const bool xin0 = x0 >= 0 && x0 < P.W, xin1 = x1 >= 0 && x1 < P.W;
-            const bool yin0 = y0 >= 0 && y0 < P.H, yin1 = y1 >= 0 && y1 < P.H;
             const unsigned long long id = (unsigned long long)(i * 4);
             if (inr) {
                 if (yin0 && xin0) { kk[0] = ((unsigned long long)((size_t)y0 * P.W + x0) << 32) | id; vv[0] = go * wx0 * wy0; }
@@ -669,6 +721,37 @@ extern "C" int sassd_pswarp_sample(const float *feat, int batch, int H, int W, c
     linspace_f32(-0.5f, 0.5f, 4, P.lin4);
     linspace_f32(-0.5f, 0.5f, 7, P.lin7);
     hipLaunchKernelGGL(pswarp_kernel, dim3(cdiv(capK, 8), batch), dim3(256), 0, (hipStream_t)stream_, P);
+    return sassd_launch_status();
+}
+
+extern "C" size_t sassd_ps_pixel_list_ints(int batch, int H, int W)
+{
+    if (batch < 1 || H < 1 || W < 1 || (size_t)batch * H * W > ((size_t)1 << 30)) return 0;
+    const size_t HW = (size_t)H * W;
+    return ps_flag_off(batch, HW) + (size_t)batch * ps_flag_stride(HW) / 4;      // counts, lists, flag bytes
+}
+
+extern "C" int sassd_ps_pixel_list(const float *guided, const int32_t *counts, int capK, int batch, int H, int W,
+                                   float grid_off_x, float grid_off_y, float spatial_scale, int32_t *list, void *stream_)
+{
+    if (!guided || !counts || !list || capK < 1 || sassd_ps_pixel_list_ints(batch, H, W) == 0) return SASSD_EINVAL;
+    if ((uintptr_t)list & 15) return SASSD_EINVAL;
+    WarpParams P;
+    P.feat = nullptr; P.guided = guided; P.counts = counts; P.logits = nullptr;
+    P.B = batch; P.H = H; P.W = W; P.capK = capK;
+    P.offx = grid_off_x; P.offy = grid_off_y; P.scale = spatial_scale;
+    linspace_f32(-0.5f, 0.5f, 4, P.lin4);
+    linspace_f32(-0.5f, 0.5f, 7, P.lin7);
+    const int HW = H * W;
+    const int fstride = (int)ps_flag_stride(HW);
+    unsigned char *flags = (unsigned char *)(list + ps_flag_off(batch, HW));
+    hipStream_t s = (hipStream_t)stream_;
+    // (a fill KERNEL, never a memset node in a captured frame: DESIGN.md section 9) every call clears the flags itself
+    const int rc = sassd_fill2(flags, (size_t)batch * fstride, 0, flags, 0, 0, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(ps_mark_kernel, dim3(cdiv(capK, 8), batch), dim3(256), 0, s, P, flags, fstride);
+    hipLaunchKernelGGL(ps_compact_kernel, dim3(cdiv(HW, kPsBlock), batch), dim3(kPsBlock), 0, s, (const unsigned char *)flags,
+                       fstride, HW, list, list + ps_list_head(batch));
     return sassd_launch_status();
 }
 

@@ -964,6 +964,50 @@ def pswarp_sample(feat, guided, counts, cap_k, grid_offsets, spatial_scale, logi
     return logits
 
 
+def ps_pixel_list_buffer(batch, h, w, device):
+    """The int32 buffer of sassd_ps_pixel_list (counts, per-sample pixel lists, flag bytes; include/sassd.h)."""
+    n = _C.lib().sassd_ps_pixel_list_ints(int(batch), int(h), int(w))
+    if n == 0:
+        raise ValueError("ps_pixel_list: unsupported shape")
+    return torch.zeros(n, dtype=torch.int32, device=device)
+
+
+def ps_pixel_list_views(buf, batch, h, w):
+    """(counts [B] i32, pixels [B, H W] i32, flags [B, H W] u8) -- views into a ps_pixel_list_buffer."""
+    hw, head = h * w, (batch + 3) // 4 * 4
+    fs = (hw + 15) // 16 * 16
+    fo = head + (batch * hw + 3) // 4 * 4
+    flags = buf[fo:fo + batch * fs // 4].view(torch.uint8).view(batch, fs)[:, :hw]
+    return buf[:batch], buf[head:head + batch * hw].view(batch, hw), flags
+
+
+def ps_pixel_list(guided, counts, cap_k, batch, h, w, grid_offsets, spatial_scale, out=None):
+    """The pixels pswarp_sample reads for these candidates: per-sample counts and ascending pixel lists, on the device."""
+    _chk_cuda(guided, counts)
+    if out is None:
+        out = ps_pixel_list_buffer(batch, h, w, guided.device)
+    _C.check(_C.lib().sassd_ps_pixel_list(_C.ptr(guided), _C.ptr(counts), int(cap_k), int(batch), int(h), int(w),
+                                          float(grid_offsets[0]), float(grid_offsets[1]), float(spatial_scale), _C.ptr(out),
+                                          _C.stream()), "sassd_ps_pixel_list")
+    return out
+
+
+def ps_head_sampled_supported(cin, parts):
+    return bool(_C.lib().sassd_ps_head_sampled_supported(int(cin), int(parts)))
+
+
+def ps_head_sampled(x, w0_packed, scale0, shift0, relu0, w1t, scale1, shift1, relu1, pixel_list, y):
+    """The part-sensitive head (3x3 conv + 1x1 conv) at the listed pixels only, stored into the dense map `y` [B,parts,H,W]:
+    bit-identical there to conv2d_fwd(ksize 3) + conv1x1_narrow_fwd (sassd_ps_head_sampled)."""
+    _chk_cuda(x, w0_packed, scale0, shift0, w1t, scale1, shift1, pixel_list, y)
+    b, cin, h, w = x.shape
+    _C.check(_C.lib().sassd_ps_head_sampled(_C.ptr(x), _C.ptr(w0_packed), _C.ptr(scale0), _C.ptr(shift0), 1 if relu0 else 0,
+                                            _C.ptr(w1t), _C.ptr(scale1), _C.ptr(shift1), 1 if relu1 else 0,
+                                            _C.ptr(pixel_list), _C.ptr(y), b, cin, y.shape[1], h, w, _C.stream()),
+             "sassd_ps_head_sampled")
+    return y
+
+
 def pswarp_sample_bwd(feat, guided, counts, cap_k, grid_offsets, spatial_scale, dlogits, deterministic=False):
     """-> (dfeat [B,28,H,W], dguided [B,capK,7]).  deterministic: dfeat summed in ascending box order per pixel
     (sassd_pswarp_sample_bwd_det) instead of float atomics."""

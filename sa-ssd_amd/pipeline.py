@@ -16,7 +16,9 @@ Stages / reference lines:
   SSD head (fused 1x1) ssd_rotate_head.py:218-235                       sassd_conv2d_fwd
   anchors_mask         kitti.py:333-343                                 sassd_anchor_mask
   guided anchors       ssd_rotate_head.py:307-372                       sassd_decode_filter
-  PSWarp               ssd_rotate_head.py:416-447                       sassd_conv2d_fwd x2 + sassd_pswarp_sample
+  PSWarp               ssd_rotate_head.py:416-447                       sassd_conv2d_fwd x2 + sassd_pswarp_sample; the default fp32
+                                                                        plan runs the two convs at the sampled pixels only
+                                                                        (sassd_ps_pixel_list + sassd_ps_head_sampled)
   rescore + NMS        ssd_rotate_head.py:487-533                       sassd_rescore_nms
 
 precision="bf16" runs every dense conv (densify, BEVNet x8, the fused head, both part-sensitive convs) on bf16 operands with
@@ -84,7 +86,7 @@ class InferencePlan:
                  iou_thr=0.1, cap_k=4096, cap_d=512, device=None, level_cap_factor=2, overlap=True, winograd=True,
                  fused_rulebooks=True, chain_bev=True, pyramid_persistent=False, spconv_cfg=None, wino4_cfg=None,
                  skip_inactive_tiles=True, rb_sync_levels=(0, 1, 2, 3), ps_tail=False, precision="fp32",
-                 sparse_precision="fp32", dense_entry=False):
+                 sparse_precision="fp32", dense_entry=False, ps_sampled=True):
         """precision: "fp32" (default) or "bf16" (module docstring).  In bf16 mode the fp32 kernel-selection knobs
         (winograd, chain_bev, wino4_cfg, ps_tail, skip_inactive_tiles) are ignored, and a shape the bf16 kernels do not
         support raises ValueError here (there is no fp32 fall-back).
@@ -92,7 +94,13 @@ class InferencePlan:
         of `precision`; spconv_cfg selects among the fp32 sparse kernels only.
         dense_entry: False (default) -- in the fp32 / fp32-sparse plan whose conv0 runs on a tile map, conv0's Winograd input
         transform gathers the level-3 rows through a pixel -> row index grid (sassd_conv2d_wino4_chain_sparse): no dense map is
-        cleared, scattered into and read back, bit-identical.  True: the dense map of every other mode (A/B, tests)."""
+        cleared, scattered into and read back, bit-identical.  True: the dense map of every other mode (A/B, tests).
+        ps_sampled: True (default) -- a precision="fp32" plan (whatever its sparse_precision) computes the part-sensitive head
+        only at the pixels PSWarp samples: post() lists them from the frame's candidates (sassd_ps_pixel_list) and runs both
+        part-sensitive convs there (sassd_ps_head_sampled), bit-identical to the dense kernels at every pixel that is read, so
+        logits and detections are unchanged.  `ps_t` then materialises the dense maps on read.  False: the two dense launches
+        in bev_and_heads (A/B, tests).  Ignored (dense) with precision="bf16", with ps_tail=True and for head shapes the
+        sampled kernel does not take."""
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32' or 'bf16', got %r" % (precision,))
         if sparse_precision not in ("fp32", "bf16"):
@@ -158,7 +166,7 @@ class InferencePlan:
         if self.bf16:
             self._dense_weights_bf16(sd, hw, w0, w1)
         else:
-            self._dense_weights_fp32(sd, hw, w0, w1, winograd, chain_bev, wino4_cfg, ps_tail)
+            self._dense_weights_fp32(sd, hw, w0, w1, winograd, chain_bev, wino4_cfg, ps_tail, ps_sampled)
 
         # ---- anchors --------------------------------------------------------------------------------
         self.Atot = self.ncls * self.H * self.W * self.A
@@ -192,7 +200,12 @@ class InferencePlan:
         self._dense = None                                  # the [B, 64 D, H, W] map: allocated by the plans that densify
         self.act = [z(B, 256, H, W, dt=mdt) for _ in range(3)]
         self.head_out = z(B, self.head_c, H, W)
-        self.ps_t = [z(B, self.ps_parts, H, W, dt=mdt), z(B, self.ps_parts, H, W)]
+        # the part-sensitive maps (3x3 output, 1x1 output).  A sampled plan writes the second at the listed pixels only and
+        # never builds the first: `ps_t` materialises both from conv6 on read, into buffers of its own
+        self._ps_t = [None if self.ps_sampled else z(B, self.ps_parts, H, W, dt=mdt), z(B, self.ps_parts, H, W)]
+        self._ps_dense = None
+        self.ps_list = K.ps_pixel_list_buffer(B, H, W, dev) if self.ps_sampled else None
+        self.conv6 = None
         self.mask = z(B, self.Atot, dt=torch.uint8)
         self.df = dict(guided=z(B, self.capK, 7), labels=z(B, self.capK, dt=i32), scores=z(B, self.capK),
                        counts=z(B, dt=i32))
@@ -244,7 +257,7 @@ class InferencePlan:
         self.prof = None           # set to {} to collect (name, start_event, end_event) tuples per frame
         self.prof_sparse_layers = False     # with prof: also one segment per sparse conv (sparse_conv0..13)
 
-    def _dense_weights_fp32(self, sd, hw, w0, w1, winograd, chain_bev, wino4_cfg, ps_tail):
+    def _dense_weights_fp32(self, sd, hw, w0, w1, winograd, chain_bev, wino4_cfg, ps_tail, ps_sampled):
         """precision="fp32": BEVNet on Winograd / fp32-MFMA kernels with BatchNorm folded into the epilogues, the heads on the
         narrow / direct fp32 kernels."""
         D3, dev = self.D3, self.dev
@@ -295,6 +308,9 @@ class InferencePlan:
         self.ps_w0t = K.conv2d_wino4_pack_weight_narrow(w0) if self.ps_tail else None
         self.ps_narrow = K.conv1x1_narrow_supported(w1.shape[1], w1.shape[0])
         self.ps_w1 = K.conv1x1_narrow_pack_weight(w1) if self.ps_narrow else K.conv2d_pack_weight(w1)
+        # the head at the sampled pixels only (class docstring: ps_sampled): repeats the direct 3x3 kernel and the narrow 1x1
+        self.ps_sampled = bool(ps_sampled and not self.ps_tail and self.ps_narrow and w0.shape[2] == 3 and
+                               self.ps_parts == 28 and K.ps_head_sampled_supported(w0.shape[1], self.ps_parts))
 
     def _dense_weights_bf16(self, sd, hw, w0, w1):
         """precision="bf16": the raw weights of every dense conv rounded once into bf16 packs (BatchNorm stays out of them),
@@ -307,7 +323,7 @@ class InferencePlan:
                                  % (what, H, W))
         need(K.densify_bf16_supported(64, self.shapes[3]), "the dense map (64 x %d channels)" % self.D3)
         self.bev, self.chain, self.wino4_ws, self.ps_tail, self.ps_w0t = [], [False] * 8, None, False, None
-        self.head_narrow = self.ps_narrow = False
+        self.head_narrow = self.ps_narrow = self.ps_sampled = False
         self.bev_cin = [int(sd["neck.fcn.conv%d.weight" % i].shape[1]) for i in range(8)]
         self.bev16 = []
         for i in range(8):
@@ -334,6 +350,20 @@ class InferencePlan:
         if self._dense is None:
             self._dense = torch.zeros(*self._dense_shape, dtype=self._dense_dt, device=self.dev)
         return self._dense
+
+    @property
+    def ps_t(self):
+        """The part-sensitive maps [3x3 output, 1x1 output] of the current frame, whole.  A sampled plan holds the second at
+        the listed pixels only: a read runs the two dense convs on the conv6 map the frame left behind, into buffers of its
+        own (inspection, tests) -- the frame path never pays for it."""
+        if not self.ps_sampled:
+            return self._ps_t
+        if self._ps_dense is None:
+            self._ps_dense = [torch.zeros(self.B, self.ps_parts, self.H, self.W, device=self.dev) for _ in range(2)]
+        if self.conv6 is not None:
+            K.conv2d_fwd(self.conv6, self.ps_w0, self.ps_parts, 3, self.ps_s0, self.ps_b0, True, self._ps_dense[0])
+            K.conv1x1_narrow_fwd(self._ps_dense[0], self.ps_w1, self.ps_parts, None, None, False, self._ps_dense[1])
+        return self._ps_dense
 
     @property
     def dense(self):
@@ -539,7 +569,7 @@ class InferencePlan:
                 # conv6's products stay in the workspace: the tail call stores conv6's activation map (for conv7) and runs the
                 # part-sensitive 3x3 conv on them
                 K.conv2d_wino4_chain_tail(self.bev[6][3:5] + (True,), y, self.ps_w0t, cout, self.ps_parts, self.cmax, self.B,
-                                          self.H, self.W, self.ps_s0, self.ps_b0, True, self.ps_t[0], self.wino4_ws,
+                                          self.H, self.W, self.ps_s0, self.ps_b0, True, self._ps_t[0], self.wino4_ws,
                                           cfg=self.wino4_cfg)
             self._seg("bev_conv%d" % i, e0)
             x = y
@@ -551,12 +581,15 @@ class InferencePlan:
             K.conv1x1_narrow_fwd(x, self.head_w, self.head_c, None, self.head_b, False, self.head_out)
         else:
             K.conv2d_fwd(x, self.head_w, self.head_c, 1, None, self.head_b, False, self.head_out)
+        if self.ps_sampled:             # post() runs both part-sensitive convs, at the pixels the candidates sample
+            self._seg("heads", e0)
+            return
         if not self.ps_tail:
-            K.conv2d_fwd(self.conv6, self.ps_w0, self.ps_parts, 3, self.ps_s0, self.ps_b0, True, self.ps_t[0])
+            K.conv2d_fwd(self.conv6, self.ps_w0, self.ps_parts, 3, self.ps_s0, self.ps_b0, True, self._ps_t[0])
         if self.ps_narrow:
-            K.conv1x1_narrow_fwd(self.ps_t[0], self.ps_w1, self.ps_parts, None, None, False, self.ps_t[1])
+            K.conv1x1_narrow_fwd(self._ps_t[0], self.ps_w1, self.ps_parts, None, None, False, self._ps_t[1])
         else:
-            K.conv2d_fwd(self.ps_t[0], self.ps_w1, self.ps_parts, 1, None, None, False, self.ps_t[1])
+            K.conv2d_fwd(self._ps_t[0], self.ps_w1, self.ps_parts, 1, None, None, False, self._ps_t[1])
         self._seg("heads", e0)
 
     def _bev_and_heads_bf16(self):
@@ -575,8 +608,8 @@ class InferencePlan:
         self.x = x
         e0 = self._ev() if self.prof is not None else None
         K.conv1x1_bf16_infer_fwd(x, self.head_w, self.head_c, None, self.head_b, False, self.head_out, out_bf16=False)
-        K.conv2d_bf16_infer_fwd(self.conv6, self.ps_w0, self.ps_parts, self.ps_s0, self.ps_b0, True, self.ps_t[0])
-        K.conv1x1_bf16_infer_fwd(self.ps_t[0], self.ps_w1, self.ps_parts, None, None, False, self.ps_t[1], out_bf16=False)
+        K.conv2d_bf16_infer_fwd(self.conv6, self.ps_w0, self.ps_parts, self.ps_s0, self.ps_b0, True, self._ps_t[0])
+        K.conv1x1_bf16_infer_fwd(self._ps_t[0], self.ps_w1, self.ps_parts, None, None, False, self._ps_t[1], out_bf16=False)
         self._seg("heads", e0)
 
     def anchor_masks(self, masks=None):
@@ -597,7 +630,12 @@ class InferencePlan:
         dirp = base[(self.n_box + self.n_cls) * HW:]
         K.decode_filter(box, cls, dirp, self.head_c * HW, self.B, self.ncls, self.A, self.H, self.W, self.anchors,
                         self.mask, self.rpn_thr, self.capK, self.df, self.status)
-        K.pswarp_sample(self.ps_t[1], self.df["guided"], self.df["counts"], self.capK, self.grid_offsets,
+        if self.ps_sampled:
+            K.ps_pixel_list(self.df["guided"], self.df["counts"], self.capK, self.B, self.H, self.W, self.grid_offsets,
+                            self.spatial_scale, out=self.ps_list)
+            K.ps_head_sampled(self.conv6, self.ps_w0, self.ps_s0, self.ps_b0, True, self.ps_w1, None, None, False,
+                              self.ps_list, self._ps_t[1])
+        K.pswarp_sample(self._ps_t[1], self.df["guided"], self.df["counts"], self.capK, self.grid_offsets,
                         self.spatial_scale, self.logits)
         K.rescore_nms(self.df["guided"], self.logits, self.df["labels"], self.df["counts"], self.score_thr,
                       self.iou_thr, self.capD, self.det, self.status)
