@@ -858,7 +858,15 @@ int sassd_noise_per_box(const float *boxes, const uint8_t *valid, const double *
  * sassd_adam_step:  g' = grad * grad_scale * min(1, max_norm / (sqrt(sumsq) * grad_scale + 1e-6)) when grad_sumsq is
  *                   non-NULL and max_norm > 0 (torch clip_grad_norm_ semantics), else grad * grad_scale;
  *                   p *= 1 - wd*lr; m,v Adam moments; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps).
- *                   `step` is t >= 1.  All pointers 16-byte aligned. */
+ *                   `step` is t >= 1.  All pointers 16-byte aligned.
+ * The other two optimizer types of optimization/__init__.py:9-16 take the same g' (the clip acts on the raw gradient,
+ * before weight decay, as clip_grad_norm_ does in front of optimizer.step()) over the same flat buffers:
+ * sassd_adam_l2_step: 'adam' = torch Adam(weight_decay): g = g' + wd*p; m, v, and the bias-corrected update as above
+ *                   on g; there is no p *= 1 - wd*lr.  Same arguments and checks as sassd_adam_step.
+ * sassd_sgd_step:   'sgd' = torch SGD(momentum, weight_decay), no dampening, no Nesterov: g = g' + wd*p;
+ *                   buf = momentum*buf + g; p -= lr*buf.  A zero-initialised buffer gives torch's first step
+ *                   (buf = g).  12 B read + 8 B written per element.
+ * Both: SASSD_EINVAL for a NULL or not 16-byte aligned param / grad / state pointer and for n < 0. */
 /* Training-mode BatchNorm1d + ReLU of the sparse blocks (cmn.py:147-173: SubMConv3d / SparseConv3d -> BatchNorm1d(eps
  * 1e-3, momentum 0.01) -> ReLU) over features x [n, C] row-major, two launches each way instead of torch's six.
  *   fwd: y = relu((x - mean) * invstd * gamma + beta) with batch statistics (biased variance); save_mean / save_invstd [C]
@@ -957,6 +965,11 @@ int sassd_grad_sumsq(const float *grad, long n, float *out, void *stream);
 int sassd_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n,
                     const float *grad_sumsq, float lr, float beta1, float beta2, float eps, float weight_decay,
                     int step, float max_norm, float grad_scale, void *stream);
+int sassd_adam_l2_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n,
+                       const float *grad_sumsq, float lr, float beta1, float beta2, float eps, float weight_decay,
+                       int step, float max_norm, float grad_scale, void *stream);
+int sassd_sgd_step(float *param, const float *grad, float *momentum_buf, long n, const float *grad_sumsq, float lr,
+                   float momentum, float weight_decay, float max_norm, float grad_scale, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Deterministic training (opt-in: train_cfg['deterministic'] or torch.use_deterministic_algorithms(True)).

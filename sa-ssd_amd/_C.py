@@ -200,6 +200,8 @@ _SIGS = {
     "sassd_gather_pack": (_I, [_P, _P, _P, C.c_long, _I, _P]),
     "sassd_grad_sumsq": (_I, [_P, C.c_long, _P, _P]),
     "sassd_adam_step": (_I, [_P, _P, _P, _P, C.c_long, _P, _F, _F, _F, _F, _F, _I, _F, _F, _P]),
+    "sassd_adam_l2_step": (_I, [_P, _P, _P, _P, C.c_long, _P, _F, _F, _F, _F, _F, _I, _F, _F, _P]),
+    "sassd_sgd_step": (_I, [_P, _P, _P, C.c_long, _P, _F, _F, _F, _F, _F, _P]),
     "sassd_mfma_probe": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
     # deterministic training mode (include/sassd.h "Deterministic training")
     "sassd_three_interpolate_grad_det_workspace_bytes": (_SZ, [_I, _I]),

@@ -3,6 +3,8 @@
 // fastai_optim.py:132-148: decoupled weight decay p *= 1 - wd*lr on every group, then torch Adam with
 // weight_decay 0, betas (mom, 0.99)) over ONE flat fp32 parameter / gradient buffer.
 // HBM-bound streaming kernels: 5.34 M parameters -> 16 B read + 12 B written per element, float4 accesses.
+// The other two optimizer types of optimization/__init__.py:9-16 share the clip prologue and the layout: 'adam' (torch
+// Adam(weight_decay), the same 28 B per element) and 'sgd' (torch SGD(momentum, weight_decay): 12 B read + 8 B written).
 #include "common.h"
 
 #include <algorithm>
@@ -35,25 +37,37 @@ struct AdamArgs {
     float lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, max_norm, grad_scale;
 };
 
+// the prologue of every update kernel: 1 / world and clip_grad_norm_ as one factor on the raw gradient
+__device__ __forceinline__ float clip_coef(const float *__restrict__ sumsq, float max_norm, float grad_scale)
+{
+    float coef = grad_scale;
+    if (sumsq && max_norm > 0.f) {
+        const float norm = sqrtf(*sumsq) * grad_scale;
+        coef *= fminf(1.f, max_norm / (norm + 1e-6f));
+    }
+    return coef;
+}
+
+// L2 = false: 'adam_onecycle' (decoupled decay p *= 1 - wd*lr, then Adam with weight_decay 0)
+// L2 = true:  'adam' (torch Adam(weight_decay): the decay joins the gradient, the parameter is not scaled)
+template <bool L2>
 __device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, const AdamArgs &a, float coef)
 {
     g *= coef;
-    p *= 1.f - a.wd * a.lr;
+    if (L2) g += a.wd * p;
+    else p *= 1.f - a.wd * a.lr;
     m = a.beta1 * m + (1.f - a.beta1) * g;
     v = a.beta2 * v + (1.f - a.beta2) * g * g;
     const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
     p -= (a.lr / a.bc1) * (m / denom);
 }
 
+template <bool L2>
 __global__ void __launch_bounds__(256) adam_kernel(float *__restrict__ p, const float *__restrict__ g,
                                                    float *__restrict__ m, float *__restrict__ v, long n,
                                                    const float *__restrict__ sumsq, AdamArgs a)
 {
-    float coef = a.grad_scale;
-    if (sumsq && a.max_norm > 0.f) {
-        const float norm = sqrtf(*sumsq) * a.grad_scale;
-        coef *= fminf(1.f, a.max_norm / (norm + 1e-6f));
-    }
+    const float coef = clip_coef(sumsq, a.max_norm, a.grad_scale);
     const long n4 = n >> 2;
     f32x4 *p4 = reinterpret_cast<f32x4 *>(p), *m4 = reinterpret_cast<f32x4 *>(m), *v4 = reinterpret_cast<f32x4 *>(v);
     const f32x4 *g4 = reinterpret_cast<const f32x4 *>(g);
@@ -63,15 +77,71 @@ __global__ void __launch_bounds__(256) adam_kernel(float *__restrict__ p, const 
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             float ps = pp[c], ms = mm[c], vs = vv[c];
-            adam_one(ps, gg[c], ms, vs, a, coef);
+            adam_one<L2>(ps, gg[c], ms, vs, a, coef);
             pp[c] = ps; mm[c] = ms; vv[c] = vs;
         }
         p4[i] = pp; m4[i] = mm; v4[i] = vv;
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const long i = (n4 << 2) + threadIdx.x;
-        adam_one(p[i], g[i], m[i], v[i], a, coef);
+        adam_one<L2>(p[i], g[i], m[i], v[i], a, coef);
     }
+}
+
+// torch SGD(momentum, weight_decay), no dampening, no Nesterov: a zero buffer gives torch's first step (buf = g)
+struct SgdArgs {
+    float lr, momentum, wd, max_norm, grad_scale;
+};
+
+__device__ __forceinline__ void sgd_one(float &p, float g, float &b, const SgdArgs &a, float coef)
+{
+    g = g * coef + a.wd * p;
+    b = a.momentum * b + g;
+    p -= a.lr * b;
+}
+
+__global__ void __launch_bounds__(256) sgd_kernel(float *__restrict__ p, const float *__restrict__ g,
+                                                  float *__restrict__ b, long n, const float *__restrict__ sumsq,
+                                                  SgdArgs a)
+{
+    const float coef = clip_coef(sumsq, a.max_norm, a.grad_scale);
+    const long n4 = n >> 2;
+    f32x4 *p4 = reinterpret_cast<f32x4 *>(p), *b4 = reinterpret_cast<f32x4 *>(b);
+    const f32x4 *g4 = reinterpret_cast<const f32x4 *>(g);
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        f32x4 pp = p4[i], bb = b4[i];
+        const f32x4 gg = g4[i];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            float ps = pp[c], bs = bb[c];
+            sgd_one(ps, gg[c], bs, a, coef);
+            pp[c] = ps; bb[c] = bs;
+        }
+        p4[i] = pp; b4[i] = bb;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = (n4 << 2) + threadIdx.x;
+        sgd_one(p[i], g[i], b[i], a, coef);
+    }
+}
+
+int update_blocks(long n) { return (int)std::min<long>(2048, std::max<long>(1, (n / 4 + 255) / 256)); }
+
+template <bool L2>
+int adam_launch(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n, const float *grad_sumsq,
+                float lr, float beta1, float beta2, float eps, float weight_decay, int step, float max_norm,
+                float grad_scale, void *stream_)
+{
+    if (!param || !grad || !exp_avg || !exp_avg_sq || n < 0 || step < 1) return SASSD_EINVAL;
+    if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return SASSD_EINVAL;
+    AdamArgs a;
+    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay;
+    a.bc1 = (float)(1.0 - std::pow((double)beta1, (double)step));
+    a.bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)beta2, (double)step));
+    a.max_norm = max_norm; a.grad_scale = grad_scale;
+    hipLaunchKernelGGL(adam_kernel<L2>, dim3(update_blocks(n)), dim3(256), 0, (hipStream_t)stream_, param, grad, exp_avg,
+                       exp_avg_sq, n, grad_sumsq, a);
+    return sassd_launch_status();
 }
 }  // namespace
 
@@ -147,16 +217,28 @@ extern "C" int sassd_adam_step(float *param, const float *grad, float *exp_avg, 
                                const float *grad_sumsq, float lr, float beta1, float beta2, float eps,
                                float weight_decay, int step, float max_norm, float grad_scale, void *stream_)
 {
-    if (!param || !grad || !exp_avg || !exp_avg_sq || n < 0 || step < 1) return SASSD_EINVAL;
-    if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return SASSD_EINVAL;
-    AdamArgs a;
-    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay;
-    a.bc1 = (float)(1.0 - std::pow((double)beta1, (double)step));
-    a.bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)beta2, (double)step));
-    a.max_norm = max_norm; a.grad_scale = grad_scale;
-    const int blocks = (int)std::min<long>(2048, std::max<long>(1, (n / 4 + 255) / 256));
-    hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, param, grad, exp_avg,
-                       exp_avg_sq, n, grad_sumsq, a);
+    return adam_launch<false>(param, grad, exp_avg, exp_avg_sq, n, grad_sumsq, lr, beta1, beta2, eps, weight_decay, step,
+                              max_norm, grad_scale, stream_);
+}
+
+extern "C" int sassd_adam_l2_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long n,
+                                  const float *grad_sumsq, float lr, float beta1, float beta2, float eps,
+                                  float weight_decay, int step, float max_norm, float grad_scale, void *stream_)
+{
+    return adam_launch<true>(param, grad, exp_avg, exp_avg_sq, n, grad_sumsq, lr, beta1, beta2, eps, weight_decay, step,
+                             max_norm, grad_scale, stream_);
+}
+
+extern "C" int sassd_sgd_step(float *param, const float *grad, float *momentum_buf, long n, const float *grad_sumsq,
+                              float lr, float momentum, float weight_decay, float max_norm, float grad_scale,
+                              void *stream_)
+{
+    if (!param || !grad || !momentum_buf || n < 0) return SASSD_EINVAL;
+    if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)momentum_buf) & 15) return SASSD_EINVAL;
+    SgdArgs a;
+    a.lr = lr; a.momentum = momentum; a.wd = weight_decay; a.max_norm = max_norm; a.grad_scale = grad_scale;
+    hipLaunchKernelGGL(sgd_kernel, dim3(update_blocks(n)), dim3(256), 0, (hipStream_t)stream_, param, grad,
+                       momentum_buf, n, grad_sumsq, a);
     return sassd_launch_status();
 }
 

@@ -1278,6 +1278,22 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, sumsq, lr, beta1, beta2, eps, we
                                       max_norm, grad_scale, _C.stream()), "sassd_adam_step")
 
 
+def adam_l2_step(param, grad, exp_avg, exp_avg_sq, sumsq, lr, beta1, beta2, eps, weight_decay, step, max_norm=0.0,
+                 grad_scale=1.0):
+    """In-place fused clip + torch Adam(weight_decay) update (the decay joins the gradient) over flat fp32 buffers."""
+    _chk_cuda(param, grad, exp_avg, exp_avg_sq)
+    _C.check(_C.lib().sassd_adam_l2_step(_C.ptr(param), _C.ptr(grad), _C.ptr(exp_avg), _C.ptr(exp_avg_sq),
+                                         param.numel(), _C.ptr(sumsq), lr, beta1, beta2, eps, weight_decay, int(step),
+                                         max_norm, grad_scale, _C.stream()), "sassd_adam_l2_step")
+
+
+def sgd_step(param, grad, momentum_buf, sumsq, lr, momentum, weight_decay, max_norm=0.0, grad_scale=1.0):
+    """In-place fused clip + torch SGD(momentum, weight_decay) update over flat fp32 buffers."""
+    _chk_cuda(param, grad, momentum_buf)
+    _C.check(_C.lib().sassd_sgd_step(_C.ptr(param), _C.ptr(grad), _C.ptr(momentum_buf), param.numel(), _C.ptr(sumsq),
+                                     lr, momentum, weight_decay, max_norm, grad_scale, _C.stream()), "sassd_sgd_step")
+
+
 def rotate_iou_eval(boxes, query_boxes, criterion=-1):
     """boxes [N,5], query_boxes [K,5] (cx, cy, x_dim, y_dim, angle) device tensors -> [N,K] overlap matrix of the KITTI
     evaluation (criterion -1 IoU, 0 / 1 intersection over the query's / the box's area)."""

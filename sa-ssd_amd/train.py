@@ -7,10 +7,14 @@
   * AdamOneCycle    optimizer type 'adam_onecycle' (optimization/__init__.py:17-30; fastai_optim.py:101-148:
                     Adam(betas=(mom, 0.99)), true weight decay on every group incl. BatchNorm) + clip_grad_norm_
                     (train_utils/__init__.py:60) fused in sassd_grad_sumsq / sassd_adam_step.
+  * Adam / SGD      optimizer types 'adam' and 'sgd' (optimization/__init__.py:10-16) on the same flat buffers
+                    (sassd_adam_l2_step / sassd_sgd_step); FlatOptimizer is what the three share.
+  * CosineLR / MultiStepLR   lr policies 'cosine' and 'step' (optimization/__init__.py:47-52), by iteration.
   * GradSync        one process per GPU; parameters broadcast from rank 0 once, gradients all-reduced (sum; the 1/world
                     mean is folded into the update kernel's grad_scale).  BatchNorm stays per-GPU like the reference.
   * train_one_iter / checkpoint_state / save / load   train_utils/__init__.py:36-66,120-170.
 """
+import bisect
 import math
 
 import torch
@@ -245,17 +249,24 @@ class CosineWarmupLR:
         self.optimizer.lr = self.eta_min + (self.base_lr - self.eta_min) * (1 - math.cos(math.pi * step / self.T_max)) / 2
 
 
-class AdamOneCycle:
-    def __init__(self, model, lr, weight_decay, beta2=0.99, eps=1e-8, grad_clip=None, world_size=1, deterministic=False):
+class FlatOptimizer:
+    """What the optimizer types share around their update kernel: the flat buffers, clip_grad_norm_ (L2) as one square
+    sum, world_size as the kernel's grad_scale, the deterministic square sum, the weight-image generation and the
+    PackPlan run after the raw-pointer update.  A subclass names its `type`, its flat state tensors (`state_keys`) and
+    launches its kernel in `_update`."""
+    type = None
+    state_keys = ()
+
+    def __init__(self, model, lr, weight_decay, grad_clip=None, world_size=1, deterministic=False):
         self.flat = model if isinstance(model, FlatParams) else FlatParams(model)
-        self.lr, self.mom, self.wd, self.beta2, self.eps = lr, 0.9, weight_decay, beta2, eps
+        self.lr, self.wd = lr, weight_decay
         self.max_norm = float(grad_clip["max_norm"]) if grad_clip else 0.0
         if grad_clip and grad_clip.get("norm_type", 2) != 2:
             raise NotImplementedError("only the L2 gradient-norm clip of the reference configs")
         self.world_size = world_size
         self.deterministic = bool(deterministic)   # the clip's square sum in a length-only order (sassd_grad_sumsq_det)
-        self.exp_avg = torch.zeros_like(self.flat.data)
-        self.exp_avg_sq = torch.zeros_like(self.flat.data)
+        for k in self.state_keys:
+            setattr(self, k, torch.zeros_like(self.flat.data))
         self.sumsq = torch.zeros(1, dtype=torch.float32, device=self.flat.data.device)
         self.steps = 0
         self.pack_plan = None                 # PackPlan(model, self.flat): all weight images re-packed in one launch
@@ -267,21 +278,87 @@ class AdamOneCycle:
         self.steps += 1
         grad = self.flat.grad                                 # gathers this step's gradients (one multi-tensor copy)
         sumsq = K.grad_sumsq(grad, self.sumsq, deterministic=self.deterministic) if self.max_norm > 0 else None
-        K.adam_step(self.flat.data, grad, self.exp_avg, self.exp_avg_sq, sumsq, self.lr, self.mom,
-                    self.beta2, self.eps, self.wd, self.steps, self.max_norm, 1.0 / self.world_size)
+        self._update(grad, sumsq, 1.0 / self.world_size)
         K.bump_weights_generation()          # raw-pointer update: parameter `_version`s did not move
         if self.pack_plan is not None:
             self.pack_plan.run()
+
+    def _update(self, grad, sumsq, grad_scale):
+        raise NotImplementedError
+
+    def state_dict(self):
+        sd = dict(type=self.type, steps=self.steps, lr=self.lr)
+        sd.update({k: getattr(self, k).clone() for k in self.state_keys})
+        return sd
+
+    def _check_state(self, sd):
+        """ValueError unless `sd` is a flat state of this optimizer's type and size (nothing is copied before)."""
+        kind = sd.get("type", "adam_onecycle" if "exp_avg" in sd else None)     # (an 'adam_onecycle' state carries no type key)
+        if kind != self.type:
+            raise ValueError("optimizer state of type %r cannot be loaded into a %r optimizer" % (kind, self.type))
+        for k in self.state_keys:
+            if k not in sd or tuple(sd[k].shape) != tuple(getattr(self, k).shape):
+                raise ValueError("%r optimizer state: %r is missing or is not a flat [%d] buffer"
+                                 % (self.type, k, self.flat.numel))
+
+    def load_state_dict(self, sd):
+        self._check_state(sd)
+        for k in self.state_keys:
+            getattr(self, k).copy_(sd[k])
+        self.steps, self.lr = sd["steps"], sd["lr"]
+        K.bump_weights_generation()
+
+
+class AdamOneCycle(FlatOptimizer):
+    type = "adam_onecycle"
+    state_keys = ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, model, lr, weight_decay, beta2=0.99, eps=1e-8, grad_clip=None, world_size=1, deterministic=False):
+        super().__init__(model, lr, weight_decay, grad_clip, world_size, deterministic)
+        self.mom, self.beta2, self.eps = 0.9, beta2, eps
+
+    def _update(self, grad, sumsq, grad_scale):
+        K.adam_step(self.flat.data, grad, self.exp_avg, self.exp_avg_sq, sumsq, self.lr, self.mom,
+                    self.beta2, self.eps, self.wd, self.steps, self.max_norm, grad_scale)
 
     def state_dict(self):
         return dict(exp_avg=self.exp_avg.clone(), exp_avg_sq=self.exp_avg_sq.clone(), steps=self.steps, lr=self.lr,
                     mom=self.mom)
 
     def load_state_dict(self, sd):
-        self.exp_avg.copy_(sd["exp_avg"])
-        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
-        self.steps, self.lr, self.mom = sd["steps"], sd["lr"], sd["mom"]
-        K.bump_weights_generation()
+        super().load_state_dict(sd)
+        self.mom = sd["mom"]
+
+
+class Adam(FlatOptimizer):
+    """optimizer type 'adam' (optimization/__init__.py:10-11): torch Adam(lr, weight_decay), betas (0.9, 0.999), eps 1e-8
+    -- the decay joins the gradient (sassd_adam_l2_step)."""
+    type = "adam"
+    state_keys = ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, model, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8, grad_clip=None, world_size=1,
+                 deterministic=False):
+        super().__init__(model, lr, weight_decay, grad_clip, world_size, deterministic)
+        self.betas, self.eps = tuple(betas), eps
+
+    def _update(self, grad, sumsq, grad_scale):
+        K.adam_l2_step(self.flat.data, grad, self.exp_avg, self.exp_avg_sq, sumsq, self.lr, self.betas[0],
+                       self.betas[1], self.eps, self.wd, self.steps, self.max_norm, grad_scale)
+
+
+class SGD(FlatOptimizer):
+    """optimizer type 'sgd' (optimization/__init__.py:12-16): torch SGD(lr, weight_decay, momentum), no dampening, no
+    Nesterov (sassd_sgd_step).  The zero-initialised buffer gives torch's first step."""
+    type = "sgd"
+    state_keys = ("momentum_buffer",)
+
+    def __init__(self, model, lr, weight_decay, momentum, grad_clip=None, world_size=1, deterministic=False):
+        super().__init__(model, lr, weight_decay, grad_clip, world_size, deterministic)
+        self.momentum = momentum
+
+    def _update(self, grad, sumsq, grad_scale):
+        K.sgd_step(self.flat.data, grad, self.momentum_buffer, sumsq, self.lr, self.momentum, self.wd, self.max_norm,
+                   grad_scale)
 
 
 def resolve_deterministic(model, deterministic=None):
@@ -294,21 +371,60 @@ def resolve_deterministic(model, deterministic=None):
 
 
 def build_optimizer(model, optim_cfg, world_size=1, deterministic=None):
-    if optim_cfg["type"] != "adam_onecycle":
-        raise NotImplementedError("the SA-SSD configs train with 'adam_onecycle'")
-    opt = AdamOneCycle(model, optim_cfg["lr"], optim_cfg["weight_decay"], grad_clip=optim_cfg.get("grad_clip"),
-                       world_size=world_size, deterministic=resolve_deterministic(model, deterministic))
+    """optimization/__init__.py:9-34: 'adam' | 'sgd' | 'adam_onecycle'."""
+    common = dict(grad_clip=optim_cfg.get("grad_clip"), world_size=world_size,
+                  deterministic=resolve_deterministic(model, deterministic))
+    if optim_cfg["type"] == "adam_onecycle":
+        opt = AdamOneCycle(model, optim_cfg["lr"], optim_cfg["weight_decay"], **common)
+    elif optim_cfg["type"] == "adam":
+        opt = Adam(model, optim_cfg["lr"], optim_cfg["weight_decay"], **common)
+    elif optim_cfg["type"] == "sgd":
+        opt = SGD(model, optim_cfg["lr"], optim_cfg["weight_decay"], optim_cfg["momentum"], **common)
+    else:
+        raise NotImplementedError("optimizer type %r (the reference builds 'adam', 'sgd' and 'adam_onecycle')"
+                                  % (optim_cfg["type"],))
     if opt.flat.data.is_cuda and optim_cfg.get("pack_plan", True):
         opt.pack_plan = PackPlan(model, opt.flat)
         opt.flat.pack_plan = opt.pack_plan        # GradSync re-runs it after the parameter broadcast
     return opt
 
 
+class CosineLR:
+    """policy 'cosine' (optimization/__init__.py:47-48): the closed form of torch CosineAnnealingLR(T_max=total_step,
+    eta_min=0) stepped with the iteration number: lr = base * (1 + cos(pi * it / total_step)) / 2."""
+
+    def __init__(self, optimizer, total_step, base_lr):
+        self.optimizer, self.total_step, self.base_lr = optimizer, int(total_step), float(base_lr)
+
+    def step(self, step):
+        self.optimizer.lr = self.base_lr * (1 + math.cos(math.pi * step / self.total_step)) / 2
+
+
+class MultiStepLR:
+    """policy 'step' (optimization/__init__.py:50-52): torch MultiStepLR(milestones=lr_cfg.step, gamma=0.1) in closed
+    form.  The milestones count ITERATIONS: the reference steps the schedule with accumulated_iter."""
+
+    def __init__(self, optimizer, milestones, base_lr, gamma=0.1):
+        self.optimizer, self.milestones, self.base_lr, self.gamma = optimizer, sorted(milestones), float(base_lr), gamma
+
+    def step(self, step):
+        self.optimizer.lr = self.base_lr * self.gamma ** bisect.bisect_right(self.milestones, step)
+
+
 def build_scheduler(optimizer, total_iters_each_epoch, total_epochs, optim_cfg, lr_cfg):
-    if lr_cfg["policy"] != "onecycle":
-        raise NotImplementedError("the SA-SSD configs use the 'onecycle' policy")
-    return OneCycle(optimizer, total_iters_each_epoch * total_epochs, optim_cfg["lr"], list(lr_cfg["moms"]),
-                    lr_cfg["div_factor"], lr_cfg["pct_start"])
+    """optimization/__init__.py:37-55: 'onecycle' | 'cosine' | 'step' ('cosine' and 'step' set only .lr)."""
+    total_step = total_iters_each_epoch * total_epochs
+    if lr_cfg["policy"] == "onecycle":
+        if not hasattr(optimizer, "mom"):
+            raise ValueError("the 'onecycle' policy drives lr and momentum of 'adam_onecycle'; a %r optimizer has no "
+                             "`mom` (not a reference configuration)" % (getattr(optimizer, "type", None),))
+        return OneCycle(optimizer, total_step, optim_cfg["lr"], list(lr_cfg["moms"]), lr_cfg["div_factor"],
+                        lr_cfg["pct_start"])
+    if lr_cfg["policy"] == "cosine":
+        return CosineLR(optimizer, total_step, optim_cfg["lr"])
+    if lr_cfg["policy"] == "step":
+        return MultiStepLR(optimizer, list(lr_cfg["step"]), optim_cfg["lr"])
+    raise NotImplementedError("lr policy %r (the reference builds 'onecycle', 'cosine' and 'step')" % (lr_cfg["policy"],))
 
 
 def build_warmup_scheduler(optimizer, optim_cfg, lr_cfg):
@@ -527,9 +643,81 @@ def _copy_model_state(model, model_state):
     return loaded, skipped
 
 
+def _torch_state_param_names(model, model_state, n_groups):
+    """Which of our parameters each index of a reference torch optimizer state is, per param group, read off the
+    checkpoint's own model_state (its key order is registration order = the order of model.parameters() over there).
+    One group ('adam', 'sgd': optim.X(model.parameters())): every parameter in that order.  Two groups ('adam_onecycle':
+    OptimWrapper.create / split_bn_bias, fastai_optim.py:13-24,112-119): the trainable parameters of the non-BatchNorm
+    leaf modules, then those of the BatchNorm leaf modules -- a parameter is a BatchNorm's when model_state holds a
+    running_mean under its module prefix.  None for any other group count."""
+    sd = model.state_dict()
+    ours = dict(model.named_parameters())
+    keys = [k[len('module.'):] if k.startswith('module.') and k not in sd else k for k in model_state]
+    names = [k for k in keys if k in ours]
+    if n_groups == 1:
+        return [names]
+    if n_groups == 2:
+        keyset = set(keys)
+        is_bn = lambda k: k.rpartition('.')[0] + '.running_mean' in keyset          # noqa: E731
+        names = [k for k in names if ours[k].requires_grad]
+        return [[k for k in names if not is_bn(k)], [k for k in names if is_bn(k)]]
+    return None
+
+
+def _load_torch_optimizer_state(model, optimizer, ost, model_state):
+    """A reference checkpoint's torch optimizer state ({'state': {index: {...}}, 'param_groups': [...]}) -> the flat state
+    of `optimizer`, through the parameter views.  Everything is checked before anything is copied; -> None on success,
+    else the reason (the optimizer is then untouched)."""
+    import warnings
+    state, groups = ost.get("state"), ost.get("param_groups")
+    if not isinstance(state, dict) or not isinstance(groups, (list, tuple)) or not all(
+            isinstance(g, dict) and "params" in g for g in groups):
+        return "it matches no known shape"
+    names = _torch_state_param_names(model, model_state, len(groups))
+    if names is None or [len(g["params"]) for g in groups] != [len(n) for n in names]:
+        return "its param groups %s do not match the model's parameters %s" % (
+            [len(g["params"]) for g in groups], names and [len(n) for n in names])
+    index_of = {id(p): i for i, p in enumerate(optimizer.flat.params)}
+    ours = dict(model.named_parameters())
+    keys = optimizer.state_keys
+    todo, steps, seen = [], [], set()
+    for g, group_names in zip(groups, names):
+        for idx, name in zip(g["params"], group_names):
+            seen.add(idx)
+            entry = state.get(idx)
+            if entry is None or id(ours[name]) not in index_of:        # never received a gradient / frozen here: zeros
+                continue
+            for k in keys:
+                t = entry.get(k)
+                if not torch.is_tensor(t):
+                    return "parameter %s carries no %s (the state of another optimizer kind)" % (name, k)
+                if tuple(t.shape) != tuple(ours[name].shape):
+                    return "%s of %s has shape %s, the parameter %s" % (k, name, tuple(t.shape), tuple(ours[name].shape))
+                todo.append((k, index_of[id(ours[name])], t))
+            if "step" in entry:
+                steps.append(int(entry["step"]))                        # an int or a 0-d tensor
+    if set(state) - seen:
+        return "it holds entries for indices outside its param groups"
+    if not todo:
+        return "it carries no %s" % " / ".join(keys)
+    for k in keys:
+        getattr(optimizer, k).zero_()
+    for k, i, t in todo:
+        o, p = optimizer.flat.offsets[i], optimizer.flat.params[i]
+        getattr(optimizer, k)[o:o + p.numel()].view(p.shape).copy_(t)
+    if steps:
+        optimizer.steps = max(steps)
+        if min(steps) != max(steps):
+            warnings.warn("load_checkpoint: the per-parameter step counts of the optimizer state differ (%d..%d); the flat "
+                          "optimizer has one counter and continues from %d" % (min(steps), max(steps), max(steps)))
+    return None
+
+
 def load_checkpoint(model, optimizer, filename, map_location="cpu"):
-    """tools/train_utils/__init__.py:120-150 (resume): model + optimizer state.  A reference checkpoint carries a torch
-    Adam / OptimWrapper state dict, which has no meaning for the flat fused optimizer: it is skipped with a warning."""
+    """tools/train_utils/__init__.py:120-150 (resume): model + optimizer state.  The flat states written by this tree load
+    as they are; a reference checkpoint's torch optimizer state (Adam / SGD / OptimWrapper) is mapped onto the flat
+    buffers (_load_torch_optimizer_state).  A state that does not match the optimizer built -- another kind, other
+    parameters, an unknown shape -- is never loaded in part: a warning, and the optimizer starts fresh."""
     import warnings
     ck = torch.load(filename, map_location=map_location, weights_only=False)
     _, skipped = _copy_model_state(model, ck["model_state"])
@@ -538,11 +726,17 @@ def load_checkpoint(model, optimizer, filename, map_location="cpu"):
                                                                                         skipped[:4]))
     ost = ck.get("optimizer_state")
     if optimizer is not None and ost:
-        if isinstance(ost, dict) and "exp_avg" in ost and "exp_avg_sq" in ost:
-            optimizer.load_state_dict(ost)
-        else:
-            warnings.warn("load_checkpoint: optimizer state of %s is not in the flat exp_avg / exp_avg_sq format "
-                          "(a reference torch optimizer state?) -- optimizer starts fresh" % filename)
+        why = "it matches no known shape"
+        if isinstance(ost, dict) and "state" in ost and "param_groups" in ost:
+            why = _load_torch_optimizer_state(model, optimizer, ost, ck["model_state"])
+        elif isinstance(ost, dict) and ("exp_avg" in ost or "momentum_buffer" in ost):
+            try:
+                optimizer.load_state_dict(ost)
+                why = None
+            except ValueError as e:
+                why = str(e)
+        if why is not None:
+            warnings.warn("load_checkpoint: optimizer state of %s not loaded: %s -- optimizer starts fresh" % (filename, why))
     return ck.get("epoch", 0), ck.get("it", 0)
 
 
