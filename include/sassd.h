@@ -217,6 +217,43 @@ int sassd_spconv_bwd_weight(const float *x, const float *dy, const int32_t *nbr,
                             int cap_out, int K, int Cin, int Cout, float *dw, int accumulate, int cfg,
                             void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sparse input layer: SubMConv3d(Cin, 16, 3) for 3 <= Cin <= 8 features per voxel (csrc/spconv_in.hip).  The reference
+ * cannot run a width other than 4 (cmn.py:104-106 writes voxel_features[:, :3] into a zeros_like(voxel_features)[:, 1:]);
+ * the semantics are those of the project's oracle, oracle.nets.sparse_conv.  fp32 operands, K = 27.  The entry points of the
+ * block above keep (4, 16) and still answer SASSD_EINVAL for every other narrow width; a caller with Cin != 4 calls these.
+ * Cin = 4 is accepted here too and computes, bit for bit, what sassd_spconv_fwd computes for (4, 16).
+ *   sassd_spconv_in_supported      1 iff K == 27, 3 <= Cin <= 8 and Cout == 16.
+ *   sassd_spconv_in_pack_weight    w [K, Cin, Cout] -> an opaque image of sassd_spconv_in_packed_floats floats (0: unsupported),
+ *                                  16-byte aligned: [K][CP/4][Cout][4] with CP = Cin rounded up to a multiple of 4 and zeros
+ *                                  in the padding (at Cin = 4 the image of sassd_spconv_pack_weight).  The pack only moves
+ *                                  words.  The FEATURES are never padded: x keeps the voxelizer's row stride of Cin floats.
+ *   sassd_spconv_in_fwd            y[o, co] = act(acc * scale[co] + shift[co]) with the summation order part of the contract:
+ *                                      acc = 0;  for k = 0..26: if nbr[o, k] >= 0: for c = 0..Cin-1:
+ *                                          acc = fmaf(x[nbr[o, k]][c], w[k][c][co], acc)
+ *                                  then the epilogue of sassd_spconv_fwd (one fused multiply-add, scale / shift NULL = 1 / 0,
+ *                                  max(., 0) when relu).  y fp32 [cap_out, 16], or with y_bf16 != 0 bf16 [cap_out, 16]: the fp32
+ *                                  result rounded to bf16, nearest even, at the store (the first layer of the bf16 sparse plans).
+ *                                  The row count is read from n_out_ptr on the device, rows n..cap_out-1 of y are not written;
+ *                                  one kernel launch, no memset: capturable into a frame graph.  x and w_packed 16-byte aligned.
+ *   sassd_spconv_in_bwd_weight     dw[k][c][co] (+)= sum_{o: nbr[o,k] >= 0} x[nbr[o,k]][c] * dy[o][co]  (dw [K, Cin, Cout], dy
+ *                                  [cap_out, 16] fp32): per-workgroup partial sums over ascending rows in the caller's workspace
+ *                                  (sassd_spconv_in_bwd_weight_workspace_bytes bytes; 0: unsupported), added in a fixed order by
+ *                                  a second kernel -- two calls on the same inputs agree bit for bit.  x 16-byte aligned.
+ *                                  There is no data gradient: the input layer has none.
+ * Every entry point returns SASSD_EINVAL before any launch for a NULL pointer, an unsupported (K, Cin, Cout), a misaligned image
+ * and a workspace smaller than the size above.
+ * ---------------------------------------------------------------------------------------------- */
+int sassd_spconv_in_supported(int K, int Cin, int Cout);
+size_t sassd_spconv_in_packed_floats(int K, int Cin, int Cout);
+int sassd_spconv_in_pack_weight(const float *w, int K, int Cin, int Cout, float *packed, void *stream);
+int sassd_spconv_in_fwd(const float *x, const int32_t *nbr, const int32_t *n_out_ptr, int cap_out, const float *w_packed, int K,
+                        int Cin, int Cout, const float *scale, const float *shift, int relu, void *y, int y_bf16, void *stream);
+size_t sassd_spconv_in_bwd_weight_workspace_bytes(int cap_out, int K, int Cin, int Cout);
+int sassd_spconv_in_bwd_weight(const float *x, const float *dy, const int32_t *nbr, const int32_t *n_out_ptr, int cap_out, int K,
+                               int Cin, int Cout, float *dw, int accumulate, void *workspace, size_t workspace_bytes,
+                               void *stream);
+
 /* (a8) SparseConvTensor.dense() + view (cmn.py:112-114): out [B, C*D, H, W] f32, zero filled here.
  * channel_order 0: channel = c*D + d (reference); 1: channel = d*C + c (internal, conv0 weights permuted). */
 int sassd_densify(const float *feats, const int32_t *indices, const int32_t *n_ptr, int cap, int C,

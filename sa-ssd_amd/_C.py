@@ -64,6 +64,13 @@ _SIGS = {
     "sassd_spconv_bwd_data": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _P, _I, _P]),
     "sassd_spconv_bwd_weight_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "sassd_spconv_bwd_weight": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _SZ, _P]),
+    # sparse input layer, 3..8 features per voxel (include/sassd.h "Sparse input layer")
+    "sassd_spconv_in_supported": (_I, [_I, _I, _I]),
+    "sassd_spconv_in_packed_floats": (_SZ, [_I, _I, _I]),
+    "sassd_spconv_in_pack_weight": (_I, [_P, _I, _I, _I, _P, _P]),
+    "sassd_spconv_in_fwd": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P]),
+    "sassd_spconv_in_bwd_weight_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "sassd_spconv_in_bwd_weight": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _SZ, _P]),
     "sassd_densify": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "sassd_densify_bf16_supported": (_I, [_I, _I, _I, _I]),
     "sassd_densify_bf16": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),

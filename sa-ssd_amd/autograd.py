@@ -145,7 +145,7 @@ class SparseConvFn(Function):
         dx = dw = None
         if ctx.needs_input_grad[0]:
             if cin < 16:
-                raise NotImplementedError("sparse data gradient needs Cin >= 16 (the 4-channel input layer has none)")
+                raise NotImplementedError("sparse data gradient needs Cin >= 16 (the input layer has none)")
             on_fwd = ctx.subm and SparseConvFn.subm_on_forward_table and n_in > 0
             wt = _spconv_t_pack(weight, reverse=on_fwd)
             if nbr is None:

@@ -411,7 +411,9 @@ class SpMiddleFHD(nn.Module):
                 and all(m.features.shape[0] > 0 for m in middle)
                 and [m.features.shape[1] for m in middle] == [32, 64, 64]):
             return x, conv6, ((voxel_features, coors, middle, batch_size), None, None)
-        points_mean = torch.zeros_like(voxel_features)
+        # [batch, x, y, z] of the voxel means: columns 0..2 of the features, whatever their width (the reference's
+        # zeros_like(voxel_features), cmn.py:104-106, is this at width 4 and fits no other width)
+        points_mean = voxel_features.new_zeros(voxel_features.shape[0], 4)
         points_mean[:, 0] = coors[:, 0]
         points_mean[:, 1:] = voxel_features[:, :3]
         ps = []

@@ -317,10 +317,61 @@ def rulebook_pairs(nbr, n_out_ptr, cap_out):
 
 
 # --------------------------------------------------------------------------------------------------
+def spconv_in_routed(k, cin, cout):
+    """The sparse input layer at a width other than 4 -- SubMConv3d(Cin, 16, 3), Cin in 3..8 -- runs on the sassd_spconv_in_* entry
+    points (csrc/spconv_in.hip); the wrappers below route it there.  Width 4 stays on the calls it always took."""
+    return k == 27 and 3 <= cin <= 8 and cin != 4 and cout == 16
+
+
+def spconv_in_pack_weight(w):
+    """w [27, Cin, 16] f32 -> the input layer's image [27][CP/4][16][4] (CP = Cin rounded up to a multiple of 4, zero padding)."""
+    _chk_cuda(w)
+    k, cin, cout = w.shape
+    L = _C.lib()
+    n = L.sassd_spconv_in_packed_floats(k, cin, cout)
+    if not n:
+        raise ValueError("no sparse input-layer kernel for K=%d, %d -> %d" % (k, cin, cout))
+    packed = torch.empty(n, dtype=torch.float32, device=w.device)
+    _C.check(L.sassd_spconv_in_pack_weight(_C.ptr(w), k, cin, cout, _C.ptr(packed), _C.stream()), "sassd_spconv_in_pack_weight")
+    return packed
+
+
+def spconv_in_fwd(x, nbr, n_out_ptr, cap_out, w_packed, k, cin, cout, scale=None, shift=None, relu=False, y=None, y_bf16=False):
+    """The input layer on the sassd_spconv_in_* kernels: x fp32 [rows, Cin] -> y [cap_out, 16] fp32, or bf16 (rounded at the store)."""
+    _chk_cuda(x, nbr, w_packed, scale, shift)
+    assert x.dtype == torch.float32 and x.shape[1] == cin
+    dt = torch.bfloat16 if y_bf16 else torch.float32
+    if y is None:
+        y = torch.empty(cap_out, cout, dtype=dt, device=x.device)
+    assert y.dtype == dt and y.is_contiguous()
+    _C.check(_C.lib().sassd_spconv_in_fwd(_C.ptr(x), _C.ptr(nbr), _C.ptr(n_out_ptr), cap_out, _C.ptr(w_packed), k, cin, cout,
+                                          _C.ptr(scale), _C.ptr(shift), 1 if relu else 0, _C.ptr(y), 1 if y_bf16 else 0,
+                                          _C.stream()), "sassd_spconv_in_fwd")
+    return y
+
+
+def spconv_in_bwd_weight(x, dy, nbr, n_out_ptr, cap_out, cin, cout, dw=None, accumulate=False):
+    """dw [27, Cin, 16] of the input layer: per-workgroup partials + a fixed-order reduction (bit-reproducible)."""
+    _chk_cuda(x, dy, nbr)
+    L = _C.lib()
+    if dw is None:
+        dw = torch.empty(27, cin, cout, dtype=torch.float32, device=x.device)
+    wsb = L.sassd_spconv_in_bwd_weight_workspace_bytes(cap_out, 27, cin, cout)
+    if not wsb:
+        raise ValueError("no sparse input-layer weight gradient for %d -> %d" % (cin, cout))
+    ws = workspace("spconv_wgrad", wsb, x.device)
+    _C.check(L.sassd_spconv_in_bwd_weight(_C.ptr(x), _C.ptr(dy), _C.ptr(nbr), _C.ptr(n_out_ptr), cap_out, 27, cin, cout,
+                                          _C.ptr(dw), 1 if accumulate else 0, _C.ptr(ws), wsb, _C.stream()),
+             "sassd_spconv_in_bwd_weight")
+    return dw
+
+
 def spconv_pack_weight(w):
     """w [K, Cin, Cout] f32 cuda (spconv layout flattened) -> packed MFMA-fragment order."""
     _chk_cuda(w)
     k, cin, cout = w.shape
+    if spconv_in_routed(k, cin, cout):
+        return spconv_in_pack_weight(w)
     packed = torch.empty(_C.lib().sassd_spconv_packed_floats(k, cin, cout), dtype=torch.float32, device=w.device)
     rc = _C.lib().sassd_spconv_pack_weight(_C.ptr(w), k, cin, cout, _C.ptr(packed), _C.stream())
     _C.check(rc, "sassd_spconv_pack_weight")
@@ -328,6 +379,8 @@ def spconv_pack_weight(w):
 
 
 def spconv_fwd(x, nbr, n_out_ptr, cap_out, w_packed, k, cin, cout, scale=None, shift=None, relu=False, y=None, cfg=None):
+    if nbr is not None and spconv_in_routed(k, cin, cout):
+        return spconv_in_fwd(x, nbr, n_out_ptr, cap_out, w_packed, k, cin, cout, scale, shift, relu, y)
     _chk_cuda(x, nbr, w_packed, scale, shift)
     if y is None:
         y = torch.empty(cap_out, cout, dtype=torch.float32, device=x.device)
@@ -365,6 +418,8 @@ def spconv_bwd_data(dy, nbrT, n_in_ptr, cap_in, wT_packed, k, cin, cout, cfg=Non
 
 
 def spconv_bwd_weight(x, dy, nbr, n_out_ptr, cap_out, cin, cout, dw=None, accumulate=False, cfg=None):
+    if spconv_in_routed(27, cin, cout):
+        return spconv_in_bwd_weight(x, dy, nbr, n_out_ptr, cap_out, cin, cout, dw, accumulate)
     _chk_cuda(x, dy, nbr)
     L = _C.lib()
     if dw is None:                                  # (the reduction kernel overwrites every element unless `accumulate`)
@@ -408,14 +463,18 @@ def densify_bf16(feats, indices, n_ptr, cap, shape, batch_size, channel_order=0,
 
 # ---- bf16 sparse backbone (InferencePlan(sparse_precision="bf16")): bf16 features, fp32 accumulation and epilogue ---------------
 def spconv_bf16_supported(k, cin, cout, cap):
+    if spconv_in_routed(k, cin, cout):              # the first layer at another width: fp32 operands, bf16 store (spconv_in_fwd)
+        return 0 < cap < (1 << 25)
     return bool(_C.lib().sassd_spconv_bf16_supported(k, cin, cout, cap))
 
 
 def spconv_bf16_pack_weight(w):
     """w [K, Cin, Cout] fp32 (raw weights, no BatchNorm folded in) -> opaque image: bf16 for Cin >= 16, the fp32 image of
-    spconv_pack_weight for the 4-channel first layer (its operands stay fp32)."""
+    spconv_pack_weight for the first layer (3..8 channels; its operands stay fp32)."""
     _chk_cuda(w)
     k, cin, cout = w.shape
+    if spconv_in_routed(k, cin, cout):
+        return spconv_in_pack_weight(w.contiguous()).view(torch.int16)
     L = _C.lib()
     nbytes = L.sassd_spconv_bf16_packed_bytes(k, cin, cout)
     if not nbytes:
@@ -427,7 +486,10 @@ def spconv_bf16_pack_weight(w):
 
 
 def spconv_fwd_bf16(x, nbr, n_out_ptr, cap_out, w_packed, k, cin, cout, scale=None, shift=None, relu=False, y=None):
-    """sparse conv with a bf16 store: x bf16 [rows, Cin] (fp32 [rows, 4] for the first layer), y bf16 [cap_out, Cout]."""
+    """sparse conv with a bf16 store: x bf16 [rows, Cin] (fp32 [rows, 3..8] for the first layer), y bf16 [cap_out, Cout]."""
+    if nbr is not None and spconv_in_routed(k, cin, cout):
+        return spconv_in_fwd(x, nbr, n_out_ptr, cap_out, w_packed.view(torch.float32), k, cin, cout, scale, shift, relu, y,
+                             y_bf16=True)
     _chk_cuda(x, nbr, w_packed, scale, shift)
     x_is_f32 = x.dtype == torch.float32
     assert x.dtype in (torch.float32, torch.bfloat16) and x.is_contiguous()

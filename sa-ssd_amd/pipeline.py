@@ -29,7 +29,7 @@ the rounding the consumer would apply at its load.  Everything else (voxelizer, 
 PSWarp sampling, rescore / NMS) and the head / part-sensitive outputs it reads stay fp32.
 
 sparse_precision="bf16" (independent of `precision`) runs the 14 sparse convs on bf16 features: sassd_spconv_fwd_bf16 with weights
-from sassd_spconv_bf16_pack_weight.  The first layer (4 -> 16, voxel means in metres) keeps fp32 operands and stores bf16; every
+from sassd_spconv_bf16_pack_weight.  The first layer (Cin -> 16, voxel means in metres) keeps fp32 operands and stores bf16; every
 other layer reads bf16 features and raw weights rounded once to bf16, accumulates in fp32, applies relu(acc * scale + shift) in
 fp32 and stores bf16.  The feature ping-pong buffers (and `middle`) hold bf16; densify copies the level-3 features unchanged into
 the bf16 map, or widens them exactly into the fp32 one (sassd_densify_from_bf16).  Voxels, rulebooks and anchor masks are those of
@@ -58,6 +58,24 @@ VXNET = [
     ("conv3.6", "conv3.7", "subm", 64, 64, "subm3"),
     ("extra_conv.0", "extra_conv.1", "1x1", 64, 64, None),
 ]
+
+
+INPUT_WEIGHT_KEY = "neck.backbone.conv0.0.weight"
+
+
+def input_features_of(state_dict):
+    """Features per voxel the detector reads: Cin of the input layer's weight [3, 3, 3, Cin, 16] (neck.num_input_features /
+    backbone.num_input_features of the config that built it).  ValueError for a missing or malformed weight and for a width
+    outside 3..8 (the sparse input-layer kernels, include/sassd.h "Sparse input layer")."""
+    w = state_dict.get(INPUT_WEIGHT_KEY)
+    if w is None:
+        raise ValueError("state dict has no %s" % INPUT_WEIGHT_KEY)
+    shape = tuple(int(s) for s in w.shape)
+    if len(shape) != 5 or shape[:3] != (3, 3, 3) or shape[4] != 16:
+        raise ValueError("%s has shape %s, expected [3, 3, 3, Cin, 16]" % (INPUT_WEIGHT_KEY, list(shape)))
+    if not 3 <= shape[3] <= 8:
+        raise ValueError("%s reads %d features per voxel; 3 to 8 are supported" % (INPUT_WEIGHT_KEY, shape[3]))
+    return shape[3]
 
 
 def fold_bn(sd, prefix, eps=BN_EPS):
@@ -117,6 +135,7 @@ class InferencePlan:
         self.grid_offsets, self.spatial_scale = grid_offsets, 1.0 / featmap_stride
         self.area_thr = anchor_area_threshold
         self.capK, self.capD = int(cap_k), int(cap_d)
+        self.cin = input_features_of(state_dict)            # features per voxel: 4 for KITTI, 3..8 supported
         sd = {k: v.detach().to(dev) for k, v in state_dict.items()}
 
         # ---- level geometry / capacities ----------------------------------------------------------
@@ -131,7 +150,9 @@ class InferencePlan:
         # ---- sparse weights -----------------------------------------------------------------------
         self.sp = []
         lvl = 0
-        for wname, bnname, kind, cin, cout, key in VXNET:
+        for li, (wname, bnname, kind, cin, cout, key) in enumerate(VXNET):
+            if li == 0:
+                cin = self.cin                              # the input layer: the table row names the KITTI width
             w = sd["neck.backbone.%s.weight" % wname].float()
             k = 1 if kind == "1x1" else 27
             lvl += kind == "down"
@@ -194,7 +215,7 @@ class InferencePlan:
                                      ("down2", 3), ("subm3", 3))}
         fdt = torch.bfloat16 if self.sparse_bf16 else f32   # sparse feature ping-pong (sparse bf16 mode: rounded at the store)
         self.feat = [z(max(self.caps), 64, dt=fdt), z(max(self.caps), 64, dt=fdt)]
-        self.mean = z(self.caps[0], 4)
+        self.mean = z(self.caps[0], self.cin)               # per-voxel means, row stride Cin (the voxelizer's nfeat)
         mdt = torch.bfloat16 if self.bf16 else f32          # maps read by a dense conv (bf16 mode: rounded at the store)
         self._dense_shape, self._dense_dt = (B, 64 * D3, H, W), mdt
         self._dense = None                                  # the [B, 64 D, H, W] map: allocated by the plans that densify
@@ -387,11 +408,14 @@ class InferencePlan:
         """clouds: list of B device tensors [Ni, ndim] f32.  Fills idx[0] (b,z,y,x), mean, row_off.  With `n_dev`
         (device int32 [B]) the clouds are capacity-sized staging buffers holding n_dev[b] points each."""
         assert len(clouds) == self.B
+        for pts in clouds:
+            if pts.shape[1] < self.cin:
+                raise ValueError("the plan reads %d features per point, a cloud has %d columns" % (self.cin, pts.shape[1]))
         e0 = self._ev() if self.prof is not None else None
         self.row_off.fill_(0)                   # (a fill KERNEL: torch's zero_() is a memset, i.e. a memset node in a captured frame)
         for b, pts in enumerate(clouds):
             K.voxelize(pts, self.voxel_size, self.pc_range, self.T, self.max_voxels, batch_idx=b, coors_cols=4,
-                       want_voxels=False, want_mean=True, nfeat=4,
+                       want_voxels=False, want_mean=True, nfeat=self.cin,
                        out=dict(coors=self.idx[0], mean=self.mean, voxel_num=self.vnum[b:b + 1],
                                 num_points=self._numpts()),
                        row_offset=self.row_off[b:b + 2], status=self.status, cap=self.caps[0],
@@ -404,8 +428,11 @@ class InferencePlan:
         return self._np
 
     def load_voxels(self, voxel_feats, coors4):
-        """Reference-style inputs (single_stage.py:110-117): mean features [M,4] and coords [M,4] (b,z,y,x)."""
+        """Reference-style inputs (single_stage.py:110-117): mean features [M,Cin] and coords [M,4] (b,z,y,x)."""
         m = voxel_feats.shape[0]
+        if voxel_feats.dim() != 2 or voxel_feats.shape[1] != self.cin:
+            raise ValueError("the plan reads %d features per voxel, got features of shape %s"
+                             % (self.cin, list(voxel_feats.shape)))
         assert m <= self.caps[0]
         self.mean[:m].copy_(voxel_feats)
         self.idx[0][:m].copy_(coors4.int())
@@ -712,6 +739,8 @@ class InferencePlan:
         KITTI annotation block of include/sassd.h behind the version 1 record.  Its input is `self.calib` [B,36] f64
         (Tr_velo_to_cam 12, R0_rect 9, P2 12, img_w, img_h, one pad per sample)."""
         dev = self.dev
+        if int(ndim) < self.cin:
+            raise ValueError("the plan reads %d features per point: capture(ndim=%d) is too narrow" % (self.cin, int(ndim)))
         if annos and not seal:
             raise ValueError("annos=True writes the annotation block into the frame record: it needs seal=True")
         self.pts_cap = int(points_cap)

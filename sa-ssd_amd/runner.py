@@ -59,7 +59,7 @@ def train_model(model, optimizer, train_loader, lr_scheduler, sync, start_epoch,
 
 
 def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=None, world=None, inflight=0,
-                points_cap=None, raw_prefix=None, device_annos=False):
+                points_cap=None, raw_prefix=None, device_annos=False, ndim=4):
     """Run the detector over `dataset` (test mode) -> list of KITTI result annotations in dataset order on every rank
     (this rank's frames are computed here, the others' gathered from their ranks).  `saveto`: also write result files.
     inflight > 0: the frames' raw points go through model.frame_stream(...) with that many frames in flight (1..4) instead of
@@ -73,7 +73,9 @@ def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=N
     keep the frame's memory and its fill kernels at the size of the reduced path.
     `device_annos` (with inflight > 0): the stream is built with annos=True and every frame is submitted with its calib and
     img_shape, so the camera-frame annotation (location, alpha, the clipped 2-D box, the keep test) is computed inside the
-    captured frame and only assembled on the host (kitti_common.result_anno_from_cam); False keeps kitti_bbox2results."""
+    captured frame and only assembled on the host (kitti_common.result_anno_from_cam); False keeps kitti_bbox2results.
+    `ndim` (with inflight > 0): float32 columns per point of the clouds the dataset loads (4: KITTI; a detector built with
+    num_input_features = 5..8 needs at least that many)."""
     if rank is None or world is None:
         rank, _, world = D.env_world() if D.dist.is_initialized() else (0, 0, 1)
     if class_names is not None:
@@ -83,7 +85,7 @@ def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=N
     annos = []
     with torch.no_grad():
         if inflight:
-            annos = _stream_test(model, dataset, mine, workers, inflight, points_cap, raw_prefix, device_annos)
+            annos = _stream_test(model, dataset, mine, workers, inflight, points_cap, raw_prefix, device_annos, ndim)
         elif device_annos:
             raise ValueError("device_annos needs inflight > 0 (the annotations are written by the captured frame of a FrameStream)")
         elif raw_prefix is not None:
@@ -100,9 +102,10 @@ def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=N
     return merged
 
 
-def _stream_test(model, dataset, indices, workers, inflight, points_cap=None, raw_prefix=None, device_annos=False):
+def _stream_test(model, dataset, indices, workers, inflight, points_cap=None, raw_prefix=None, device_annos=False, ndim=4):
     """single_test's frames through a FrameStream: the point files are read ahead on `workers` threads, submitted as host
-    clouds, and every result becomes the annotation forward_test builds for the frame's img_meta."""
+    clouds, and every result becomes the annotation forward_test builds for the frame's img_meta.  `ndim`: float32 columns
+    per point of the files and of the clouds load_frame returns (4: KITTI)."""
     from concurrent.futures import ThreadPoolExecutor
     if not dataset.with_point:
         raise ValueError("single_test(inflight > 0) feeds raw points: the dataset needs with_point=True")
@@ -111,12 +114,13 @@ def _stream_test(model, dataset, indices, workers, inflight, points_cap=None, ra
         return []
     prefix = dataset.lidar_prefix if raw_prefix is None else raw_prefix
     raw_cap = None
-    if points_cap is None or raw_prefix is not None:    # the files read below: [N, 4] float32 (kitti_common.read_lidar)
+    ndim = int(ndim)
+    if points_cap is None or raw_prefix is not None:    # the files read below: [N, ndim] float32
         sizes = [os.path.getsize(os.path.join(prefix, '%06d.bin' % dataset.sample_ids[i])) for i in indices]
-        if any(n % 16 for n in sizes):
-            raise ValueError("a point file under %s is not a whole number of 16-byte points%s"
-                             % (prefix, "" if raw_prefix is not None else ": pass points_cap"))
-        file_cap = (max(sizes) // 16 + 1023) // 1024 * 1024 or 1024        # rounded up to 1024 points
+        if any(n % (4 * ndim) for n in sizes):
+            raise ValueError("a point file under %s is not a whole number of %d-byte points%s"
+                             % (prefix, 4 * ndim, "" if raw_prefix is not None else ": pass points_cap"))
+        file_cap = (max(sizes) // (4 * ndim) + 1023) // 1024 * 1024 or 1024        # rounded up to 1024 points
         if raw_prefix is not None:
             raw_cap = file_cap
         if points_cap is None:
@@ -124,6 +128,7 @@ def _stream_test(model, dataset, indices, workers, inflight, points_cap=None, ra
     load = (dataset.load_frame, False) if raw_prefix is None else (dataset.load_frame, False, raw_prefix)
     gen = dataset.generator
     fs = model.frame_stream(dataset.anchors, inflight=inflight, points_cap=points_cap, batch_size=1, device=dataset._dev(),
+                            **({} if ndim == 4 else dict(ndim=ndim)),
                             **({} if raw_cap is None else dict(raw_cap=raw_cap)),
                             **(dict(annos=True) if device_annos else {}),
                             anchors_bv=dataset.anchors_bv, voxel_size=tuple(gen.voxel_size),

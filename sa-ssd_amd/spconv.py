@@ -185,6 +185,13 @@ class SparseConvolution(nn.Module):
         """bn: the training-mode BatchNorm1d (+ ReLU) that follows this layer in a SparseSequential; only the bf16 training path
         fuses it (the result then carries `_bn_fused`)."""
         assert isinstance(inp, SparseConvTensor)
+        if self.in_channels < 16 and self.in_channels != 4 and not (
+                self.subm and self.kernel_size == (3, 3, 3) and K.spconv_in_routed(27, self.in_channels, self.out_channels)):
+            # the input-layer kernels cover SubMConv3d(3..8, 16, 3) only: no 1x1x1 or strided form of a narrow layer
+            raise NotImplementedError("sparse conv %s (%s, %d -> %d, kernel %s): a layer of fewer than 16 input channels runs "
+                                      "as SubMConv3d(Cin, 16, 3) with Cin in 3..8 only"
+                                      % (self.indice_key or "<no indice_key>", type(self).__name__, self.in_channels,
+                                         self.out_channels, "x".join(map(str, self.kernel_size))))
         if self._bf16_train(inp):
             return self._forward_bf16(inp, bn)
         feats = inp.features_f32().contiguous().float()

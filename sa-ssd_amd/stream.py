@@ -509,7 +509,10 @@ class FrameStream:
 
     def __init__(self, state_dict, inflight=3, points_cap=None, batch_size=1, anchors=None, device=None, ndim=4,
                  raw_cap=None, annos=False, **plan_kwargs):
-        from .pipeline import InferencePlan
+        from .pipeline import InferencePlan, input_features_of
+        cin = input_features_of(state_dict)
+        if int(ndim) < cin:
+            raise ValueError("the detector reads %d features per point: FrameStream(ndim=%d) is too narrow" % (cin, int(ndim)))
         inflight = int(inflight)
         if not 1 <= inflight <= MAX_INFLIGHT:
             raise ValueError("inflight must be 1..%d, got %d" % (MAX_INFLIGHT, inflight))
