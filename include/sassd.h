@@ -35,7 +35,7 @@ extern "C" {
 #define SASSD_ST_HASH_FULL        2   /* hash table probe exhausted             */
 #define SASSD_ST_BOX_OVERFLOW     4   /* more candidate boxes than capK / capD  */
 #define SASSD_ST_GRID_SYNC        8   /* an in-launch grid barrier timed out (persistent rulebook pyramid) */
-#define SASSD_ST_POINT_OVERFLOW  16   /* more points than a point capacity (sassd_crop_polytope_dev) */
+#define SASSD_ST_POINT_OVERFLOW  16   /* more points than a point capacity (sassd_crop_polytope_dev, sassd_merge_sweeps_dev) */
 
 #define SASSD_MAX_POINTS_PER_VOXEL 64  /* max_points supported by sassd_voxelize (reference default: 35) */
 
@@ -137,6 +137,43 @@ size_t sassd_crop_polytope_workspace_bytes(int cap_in);
 int sassd_crop_polytope_dev(const float *points, int cap_in, const int32_t *n_in_dev, int ndim,
                             const double *planes, int f32_math, float *out, int cap_out, int32_t *n_out_dev,
                             int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Multi-sweep merge: the FIRST node of a captured frame whose cloud is the current sweep plus up to 15 earlier sweeps,
+ * each moved into the current sensor frame by its ego-pose transform, the time lag as an optional last feature (the
+ * nuScenes / Waymo multi-sweep input; the reference, a KITTI project, has no counterpart).  The sweeps stay in a device
+ * ring that the caller fills, one upload per sweep; a frame names the ring slots it reads through S descriptor entries
+ * in device memory, so that sassd_voxelize_dev can follow in the same graph.
+ *
+ * CONTRACT
+ *   ring       [R, sweep_cap, ndim_in] f32 device (ndim_in >= 3, xyz first).
+ *   slot, count, xform   [S] i32 device;  T [S][3][4] f64 device (row major, the fourth column the translation);  dt [S]
+ *              f32 device.  S is 1..16.  (sassd.stream.stage_layout keeps them in the frame's staging block.)
+ *   out        [cap_out, ndim_out] f32 device, ndim_out = ndim_in + (time_feature ? 1 : 0).
+ *   rows       entry s contributes c_s = clamp(count[s], 0, sweep_cap) rows, rows 0 .. c_s - 1 of ring slot slot[s].  A
+ *              slot outside [0, R) is absent: it contributes 0 rows.  Nothing is ever read outside the ring.
+ *   order      output rows in ENTRY order, entry 0 first; within an entry in ascending row order.  (The voxelizer keeps
+ *              the first max_points arrivals per voxel: the entry listed first -- the current sweep -- wins.)
+ *   transform  xform[s] == 0: all ndim_in floats of a row are copied bit for bit (the current sweep; an identity matrix
+ *              would turn -0.0 into +0.0).  xform[s] != 0: x, y, z are replaced, per row i of T[s], by
+ *                  float32(((T[s][i][0] * x + T[s][i][1] * y) + T[s][i][2] * z) + T[s][i][3])
+ *              evaluated in float64, every product and sum rounded separately in exactly this order (no fused
+ *              multiply-add, as inside_polytope of csrc/augment_core.h); the other columns are copied bit for bit.
+ *              With time_feature the last output column of every row of entry s is dt[s].
+ *   count      *n_out_dev = min(sum_s c_s, cap_out); rows of `out` at and beyond *n_out_dev are not written.
+ *   overflow   sum_s c_s > cap_out, or any count[s] > sweep_cap: SASSD_ST_POINT_OVERFLOW is OR-ed into *status; the
+ *              first cap_out rows are still written.  `status` is only ever OR-ed into.
+ *   launches   one kernel, a grid of ceil(sweep_cap / 256) x S workgroups: the shape depends on (S, sweep_cap) only.
+ *              Every thread derives its entry's first output row from the S <= 16 counts.  No host sync, no
+ *              allocation, no memset, no atomics but the OR into `status`, and no workgroup waits for another.
+ *              ndim_in == 4 without time_feature and with 16-byte aligned ring / out moves rows as 16-byte vectors;
+ *              every other case takes a strided path with the same result.
+ *   errors     SASSD_EINVAL before any HIP call: a NULL pointer (every pointer is required), S outside 1..16, R < 1,
+ *              sweep_cap < 1, cap_out < 1, ndim_in < 3, T not 8-byte aligned, another pointer not 4-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+int sassd_merge_sweeps_dev(const float *ring, int R, int sweep_cap, int ndim_in, const int32_t *slot,
+                           const int32_t *count, const int32_t *xform, const double *T, const float *dt, int S,
+                           int time_feature, float *out, int cap_out, int32_t *n_out_dev, int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * (a5) Rulebook build.  Replaces spconv v1.0 `get_indice_pairs` as invoked by SubMConv3d / SparseConv3d

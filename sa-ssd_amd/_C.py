@@ -44,6 +44,8 @@ _SIGS = {
     # frustum crop (include/sassd.h "Frustum crop")
     "sassd_crop_polytope_workspace_bytes": (_SZ, [_I]),
     "sassd_crop_polytope_dev": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _SZ, _P]),
+    # multi-sweep merge (include/sassd.h "Multi-sweep merge")
+    "sassd_merge_sweeps_dev": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P]),
     "sassd_hash_bytes": (_SZ, [_I]),
     "sassd_hash_build": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P, _P]),
     "sassd_rulebook_subm": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P, _P]),

@@ -145,6 +145,38 @@ def crop_polytope(points, n_in, planes, f32_math, out, n_out, status):
     return out, n_out
 
 
+def merge_sweeps(ring, slot, count, xform, T, dt, time_feature, out, n_out, status):
+    """The merged multi-sweep cloud of one sample (include/sassd.h "Multi-sweep merge"): the rows of `ring`
+    [R, sweep_cap, ndim_in] f32 that the S descriptor entries name -- `slot`, `count`, `xform` [S] i32, `T` [S,3,4] f64, `dt`
+    [S] f32, all on the device -- go to `out` [cap_out, ndim_in + (1 if time_feature else 0)] f32 in entry order, moved by T
+    where xform is set, their number to `n_out`; `n_out` / `status` are device int32 scalars.  One kernel launch whose shape
+    depends on (S, sweep_cap) only (graph-capturable), no workspace."""
+    _chk_cuda(ring, slot, count, xform, T, dt, out, n_out, status)
+    if ring.dim() != 3 or out.dim() != 2 or ring.shape[2] < 3 or out.shape[1] != ring.shape[2] + (1 if time_feature else 0):
+        raise ValueError("merge_sweeps: ring %s must be [R, sweep_cap, ndim_in >= 3] and out %s [rows, ndim_in%s]"
+                         % (tuple(ring.shape), tuple(out.shape), " + 1" if time_feature else ""))
+    if ring.dtype != torch.float32 or out.dtype != torch.float32:
+        raise ValueError("merge_sweeps: ring and out must be float32")
+    S = int(slot.numel())
+    if not 1 <= S <= 16:
+        raise ValueError("merge_sweeps: 1..16 descriptor entries, got %d" % S)
+    for name, t, dtype, shape in (("slot", slot, torch.int32, (S,)), ("count", count, torch.int32, (S,)),
+                                  ("xform", xform, torch.int32, (S,)), ("T", T, torch.float64, (S, 3, 4)),
+                                  ("dt", dt, torch.float32, (S,))):
+        if t.dtype != dtype or tuple(t.shape) != shape:
+            raise ValueError("merge_sweeps: %s must be %s %s, got %s %s" % (name, list(shape), dtype, tuple(t.shape), t.dtype))
+    for name, t in (("n_out", n_out), ("status", status)):
+        if t.dtype != torch.int32 or t.numel() != 1:
+            raise ValueError("merge_sweeps: %s must be one int32 word" % name)
+    if ring.shape[0] < 1 or ring.shape[1] < 1 or out.shape[0] < 1:
+        raise ValueError("merge_sweeps: ring and out need at least one row")
+    rc = _C.lib().sassd_merge_sweeps_dev(_C.ptr(ring), int(ring.shape[0]), int(ring.shape[1]), int(ring.shape[2]), _C.ptr(slot),
+                                         _C.ptr(count), _C.ptr(xform), _C.ptr(T), _C.ptr(dt), S, int(bool(time_feature)),
+                                         _C.ptr(out), int(out.shape[0]), _C.ptr(n_out), _C.ptr(status), _C.stream())
+    _C.check(rc, "sassd_merge_sweeps_dev")
+    return out, n_out
+
+
 def voxel_mean(voxels, num_points, nfeat=4):
     _chk_cuda(voxels, num_points)
     m, t, ndim = voxels.shape

@@ -247,6 +247,7 @@ class InferencePlan:
         self.graph = None
         self.record = None         # device frame record: capture(seal=True)
         self.raw_cap = None        # capture(raw_cap=...): the frame crops raw sweeps
+        self.sw_ring = None        # capture(sweeps=...): the frame merges sweeps from this device ring
         self._stage_block = None   # capture(): the frame's small inputs in one device block (sassd.stream.stage_layout)
         self._wsid = id(self)
         # coordinate-only work (rulebooks, anchors_mask) runs on a side stream, overlapping the feature path
@@ -719,7 +720,8 @@ class InferencePlan:
             return self._tail(anchors_mask)
 
     # ---- hipGraph: the whole frame as ONE launch ---------------------------------------------------------
-    def capture(self, points_cap, ndim=4, stages=("voxelize", "backbone", "tail"), seal=False, raw_cap=None, annos=False):
+    def capture(self, points_cap, ndim=4, stages=("voxelize", "backbone", "tail"), seal=False, raw_cap=None, annos=False,
+                sweeps=None):
         """Capture the frame (raw points -> detections, side stream included) into a hipGraph.  Input staging:
         `self.pts_in[b]` [points_cap, ndim] f32 and `self.npts` int32 [B]; `run_graph(clouds)` fills them and replays.
         `stages` lets a caller capture a sub-range (e.g. only the sparse backbone for a roofline measurement).
@@ -737,8 +739,28 @@ class InferencePlan:
         points_cap points sets SASSD_ST_POINT_OVERFLOW.  The block's counts are then `nraw`; `npts` is a tensor of its own.
         annos=True (needs seal=True): the frame's tail is sassd_frame_seal_kitti -- the record is layout version 2, the
         KITTI annotation block of include/sassd.h behind the version 1 record.  Its input is `self.calib` [B,36] f64
-        (Tr_velo_to_cam 12, R0_rect 9, P2 12, img_w, img_h, one pad per sample)."""
+        (Tr_velo_to_cam 12, R0_rect 9, P2 12, img_w, img_h, one pad per sample).
+        sweeps=dict(ring=<[B,R,sweep_cap,ndim_in] f32 device, shared by the plans of a stream>, S=, sweep_cap=, time_feature=):
+        the frame's cloud is merged from the ring (include/sassd.h "Multi-sweep merge").  `ndim` is the width of the MERGED
+        cloud, ndim_in + (1 if time_feature else 0), and the width check above applies to it.  The descriptors -- `self.sw_slot`,
+        `sw_count`, `sw_xform` [B,S] i32, `sw_T` [B,S,3,4] f64, `sw_dt` [B,S] f32 -- are views into the staging block; the
+        frame's first nodes are one sassd_merge_sweeps_dev per sample (one kernel each), which write `pts_in[b]` and `npts[b]`
+        for the unchanged voxelizer.  A merged cloud above points_cap sets SASSD_ST_POINT_OVERFLOW.  `npts` is a tensor of its
+        own; the block's counts are not read by the frame.  Excludes raw_cap."""
         dev = self.dev
+        S, self.sw_ring = 0, None
+        if sweeps is not None:
+            if raw_cap is not None:
+                raise ValueError("sweeps and raw_cap exclude each other: merged clouds are not cropped")
+            ring, S, tf = sweeps["ring"], int(sweeps["S"]), bool(sweeps["time_feature"])
+            if "voxelize" not in stages or not 1 <= S <= 16:
+                raise ValueError("sweeps needs 1..16 entries and the voxelize stage")
+            if (ring.dim() != 4 or ring.shape[0] != self.B or ring.shape[2] != int(sweeps["sweep_cap"])
+                    or ring.dtype != torch.float32 or not ring.is_cuda or not ring.is_contiguous()):
+                raise ValueError("sweeps: the ring must be a contiguous [B, R, sweep_cap, ndim_in] float32 device tensor")
+            ndim_out = ring.shape[3] + (1 if tf else 0)
+            if int(ndim) != ndim_out:
+                raise ValueError("sweeps: the merged cloud has %d columns, capture(ndim=%d)" % (ndim_out, int(ndim)))
         if int(ndim) < self.cin:
             raise ValueError("the plan reads %d features per point: capture(ndim=%d) is too narrow" % (self.cin, int(ndim)))
         if annos and not seal:
@@ -748,19 +770,28 @@ class InferencePlan:
         if self.raw_cap is not None and (self.raw_cap < 1 or "voxelize" not in stages):
             raise ValueError("raw_cap must be >= 1 and needs the voxelize stage")
         self.pts_in = [torch.zeros(self.pts_cap, ndim, dtype=torch.float32, device=dev) for _ in range(self.B)]
-        L = stage_layout(self.B, self.raw_cap is not None, annos, seal)
+        L = stage_layout(self.B, self.raw_cap is not None, annos, seal, **(dict(sweeps=S) if S else {}))
         block = self._stage_block = torch.zeros(L["total"], dtype=torch.uint8, device=dev)
-        counts = block[L["counts"]:L["total"]].view(torch.int32)
+        counts = block[L["counts"]:L["counts"] + 4 * self.B].view(torch.int32)
         if seal:
             self._seq = block[L["seq"]:L["counts"]].view(torch.int32)
         if annos:
-            self.calib = block[L["calib"]:L["words"]].view(torch.float64).view(self.B, CALIB_DOUBLES)
+            self.calib = block[L["calib"]:L.get("sweep_T", L["words"])].view(torch.float64).view(self.B, CALIB_DOUBLES)
         if self.raw_cap is not None:
             self.raw_in = [torch.zeros(self.raw_cap, ndim, dtype=torch.float32, device=dev) for _ in range(self.B)]
             self.crop_planes = block[L["planes"]:L["calib"]].view(torch.float64).view(self.B, 6, 4)
             self.crop_f32_math = False
             self.nraw = counts
             self.npts = torch.zeros(self.B, dtype=torch.int32, device=dev)      # written by the crop, read by the voxelizer
+        elif S:
+            self.sw_ring, self.sw_time = ring, tf
+            self.sw_T = block[L["sweep_T"]:L["words"]].view(torch.float64).view(self.B, S, 3, 4)
+            self.sw_slot, self.sw_count, self.sw_xform = (
+                block[L[k]:L[k] + 4 * self.B * S].view(torch.int32).view(self.B, S)
+                for k in ("sweep_slot", "sweep_count", "sweep_xform"))
+            self.sw_dt = block[L["sweep_dt"]:L["total"]].view(torch.float32).view(self.B, S)
+            self.sw_slot.fill_(-1)                  # until the first descriptors arrive, every entry is absent
+            self.npts = torch.zeros(self.B, dtype=torch.int32, device=dev)      # written by the merge, read by the voxelizer
         else:
             self.npts = counts
         if annos:
@@ -775,6 +806,10 @@ class InferencePlan:
                     for b in range(self.B):
                         K.crop_polytope(self.raw_in[b], self.nraw[b:b + 1], self.crop_planes[b], self.crop_f32_math,
                                         self.pts_in[b], self.npts[b:b + 1], self.status)
+                if S:
+                    for b in range(self.B):
+                        K.merge_sweeps(self.sw_ring[b], self.sw_slot[b], self.sw_count[b], self.sw_xform[b], self.sw_T[b],
+                                       self.sw_dt[b], self.sw_time, self.pts_in[b], self.npts[b:b + 1], self.status)
                 if "voxelize" in stages:
                     self.voxelize(self.pts_in, n_dev=self.npts)
                 if "backbone" in stages:
@@ -811,6 +846,8 @@ class InferencePlan:
     def stage_inputs(self, clouds):
         if self.raw_cap is not None:
             raise RuntimeError("a plan captured with raw_cap is fed through raw_in / nraw / crop_planes (sassd.stream.FrameStream)")
+        if self.sw_ring is not None:
+            raise RuntimeError("a plan captured with sweeps is fed through its ring and descriptors (sassd.stream.FrameStream)")
         for b, pts in enumerate(clouds or ()):
             n = pts.shape[0]
             if n > self.pts_cap:            # never detect on a silently truncated cloud

@@ -29,6 +29,13 @@ KITTI annotations: FrameStream(..., annos=True) ends the frame with sassd_frame_
 projection meets the image).  submit(clouds, frustums, calibs) then takes one dict(calib=..., img_shape=...) per cloud; the
 [B,36] float64 calibration block rides in the same staging block, behind the planes.  collect() returns per sample
 (boxes, scores, labels, cam); kitti_common.result_anno_from_cam turns `cam` into the result annotation by indexing alone.
+
+Multi-sweep clouds: FrameStream(..., sweeps=S, sweep_cap=N) keeps the sweeps of every sample's sequence in a device ring and
+starts the frame with sassd_merge_sweeps_dev -- one kernel per sample that merges the current sweep and the S-1 before it,
+moved into the current sensor frame by the ego pose, the time lag as the last feature.  submit(clouds, sweeps=[dict(pose=,
+time=), ...]) uploads the new sweep alone; the descriptors (ring slots, counts, transforms, lags) ride in the staging block.
+`SweepBook` is the host bookkeeping, `sweep_transform` the pose arithmetic, `merge_sweeps_host` the numpy statement of the
+kernel's contract.
 """
 from collections import deque
 
@@ -37,6 +44,7 @@ import numpy as np
 FRAME_MAGIC = 0x53460001            # SASSD_FRAME_MAGIC: 'S' 'F', layout version 1
 FRAME_MAGIC_KITTI = 0x53460002      # SASSD_FRAME_MAGIC_KITTI: layout version 2, the annotation block behind the v1 record
 CALIB_DOUBLES = 36                  # per sample: Tr_velo_to_cam 12 | R0_rect 9 | P2 12 | img_w | img_h | pad
+MAX_SWEEPS = 16                     # descriptor entries of one merged frame (sassd_merge_sweeps_dev)
 MAX_INFLIGHT = 4                    # one HIP stream per frame in flight; the runtime multiplexes a process onto 4 hardware queues
 _SEQ_MASK = 0x7FFFFFFF
 
@@ -65,29 +73,149 @@ def record_layout(B, capD, annos=False):
     return L
 
 
-def stage_layout(B, raw=False, annos=False, seal=False):
+def stage_layout(B, raw=False, annos=False, seal=False, sweeps=0):
     """Byte offsets of the frame's staging block -- its small per-frame inputs, one H2D copy -- for `B` samples:
     dict(planes, calib, words, seq, counts, total), in this order: the crop planes [B,6,4] f64 (`raw`: a frame that crops raw
     sweeps), the calibration block [B,CALIB_DOUBLES] f64 (`annos`), then the int32 words: [seq] when `seal`, counts[B] (the
     points per cloud).  A part that is absent has length 0; `seq` is None when not sealed.  The float64 parts come first, so
-    they are 8-byte aligned."""
-    B = int(B)
+    they are 8-byte aligned.
+    sweeps=S (1..MAX_SWEEPS; a frame that merges sweeps, include/sassd.h "Multi-sweep merge") adds the keys sweep_T -- the
+    transforms [B,S,3,4] f64, the last of the float64 parts, in front of `words` -- and, behind counts, sweep_slot,
+    sweep_count, sweep_xform ([B,S] i32 each) and sweep_dt ([B,S] f32); `total` covers them.  With sweeps=0 the dict is the
+    one above, key for key."""
+    B, S = int(B), int(sweeps)
     if B < 1:
         raise ValueError("no staging block for batch %d" % B)
+    if not 0 <= S <= MAX_SWEEPS:
+        raise ValueError("sweeps must be 0..%d, got %d" % (MAX_SWEEPS, S))
     calib = 8 * 6 * 4 * B if raw else 0
-    words = calib + (8 * CALIB_DOUBLES * B if annos else 0)
+    sweep_T = calib + (8 * CALIB_DOUBLES * B if annos else 0)
+    words = sweep_T + 8 * 12 * S * B
     counts = words + (4 if seal else 0)
-    return dict(planes=0, calib=calib, words=words, seq=words if seal else None, counts=counts, total=counts + 4 * B)
+    L = dict(planes=0, calib=calib, words=words, seq=words if seal else None, counts=counts, total=counts + 4 * B)
+    if S:
+        at, n = L["total"], 4 * B * S
+        L.update(sweep_T=sweep_T, sweep_slot=at, sweep_count=at + n, sweep_xform=at + 2 * n, sweep_dt=at + 3 * n,
+                 total=at + 4 * n)
+    return L
 
 
 def stage_views(buf, B, L):
     """numpy views into `buf` (uint8, at least L['total'] bytes) of the parts of L = stage_layout(B, ...):
-    dict(planes [B,6,4] f64 | None, calib [B,CALIB_DOUBLES] f64 | None, seq [1] i32 | None, counts [B] i32)."""
+    dict(planes [B,6,4] f64 | None, calib [B,CALIB_DOUBLES] f64 | None, seq [1] i32 | None, counts [B] i32), and for a
+    layout with sweeps=S also sweep_T [B,S,3,4] f64, sweep_slot / sweep_count / sweep_xform [B,S] i32, sweep_dt [B,S] f32."""
     def f64(lo, hi, *shape):
         return buf[lo:hi].view(np.float64).reshape(B, *shape) if hi > lo else None
-    return dict(planes=f64(L["planes"], L["calib"], 6, 4), calib=f64(L["calib"], L["words"], CALIB_DOUBLES),
-                seq=None if L["seq"] is None else buf[L["seq"]:L["counts"]].view(np.int32),
-                counts=buf[L["counts"]:L["total"]].view(np.int32))
+    V = dict(planes=f64(L["planes"], L["calib"], 6, 4), calib=f64(L["calib"], L.get("sweep_T", L["words"]), CALIB_DOUBLES),
+             seq=None if L["seq"] is None else buf[L["seq"]:L["counts"]].view(np.int32),
+             counts=buf[L["counts"]:L["counts"] + 4 * B].view(np.int32))
+    if "sweep_T" in L:
+        S = (L["sweep_count"] - L["sweep_slot"]) // (4 * B)
+        V["sweep_T"] = f64(L["sweep_T"], L["words"], S, 3, 4)
+        for key, end, dt in (("sweep_slot", "sweep_count", np.int32), ("sweep_count", "sweep_xform", np.int32),
+                             ("sweep_xform", "sweep_dt", np.int32), ("sweep_dt", "total", np.float32)):
+            V[key] = buf[L[key]:L[end]].view(dt).reshape(B, S)
+    return V
+
+
+def sweep_transform(pose_now, pose_then):
+    """The [3,4] float64 matrix that moves a point of the sensor frame at `pose_then` into the sensor frame at `pose_now`:
+    the upper rows of inv(pose_now) @ pose_then.  Poses are sensor-to-world 4x4 float64 RIGID transforms [R | t]; the inverse
+    is formed explicitly as [R^T | -R^T t] (exact for a rotation, no linalg.inv).  Equal poses -- a vehicle that stands --
+    give exactly [I | 0], not the rounded R^T R."""
+    a, b = np.asarray(pose_now, dtype=np.float64), np.asarray(pose_then, dtype=np.float64)
+    if a.shape != (4, 4) or b.shape != (4, 4):
+        raise ValueError("poses must be 4x4, got %s and %s" % (a.shape, b.shape))
+    out = np.zeros((3, 4))
+    if np.array_equal(a, b):
+        out[:, :3] = np.eye(3)
+        return out
+    rt = a[:3, :3].T
+    out[:, :3] = rt @ b[:3, :3]
+    out[:, 3] = rt @ b[:3, 3] + -(rt @ a[:3, 3])
+    return out
+
+
+def merge_sweeps_host(entries, time_feature):
+    """The numpy statement of sassd_merge_sweeps_dev's contract (include/sassd.h "Multi-sweep merge") for entries that are all
+    present: `entries` is a list of (points [n, ndim_in] f32, T [3,4] f64 or None, dt) in entry order -- T None is xform = 0,
+    the rows copied as they are -- -> the merged cloud [sum n, ndim_in + (1 if time_feature else 0)] f32.  What a caller
+    without FrameStream(sweeps=...) does per frame on the host."""
+    out = []
+    for pts, T, dt in entries:
+        pts = np.asarray(pts, dtype=np.float32)
+        rows = np.empty((len(pts), pts.shape[1] + (1 if time_feature else 0)), np.float32)
+        rows[:, :pts.shape[1]] = pts
+        if T is not None:
+            T = np.asarray(T, dtype=np.float64)
+            x, y, z = (pts[:, i].astype(np.float64) for i in range(3))
+            for i in range(3):                      # every product and sum rounded on its own, in the kernel's order
+                rows[:, i] = (((T[i, 0] * x + T[i, 1] * y) + T[i, 2] * z) + T[i, 3]).astype(np.float32)
+        if time_feature:
+            rows[:, -1] = np.float32(dt)
+        out.append(rows)
+    return np.ascontiguousarray(np.concatenate(out, 0))
+
+
+class SweepBook:
+    """The host bookkeeping of a stream that merges sweeps: which ring slot every sweep of a sample's sequence lives in, and
+    the poses and times the descriptors of the next frame are made of.  `plan` checks one frame's inputs and returns its
+    descriptors WITHOUT changing the book; `commit` makes them the book's state -- a refused submit leaves no trace.
+
+    Every submit writes one sweep per sample, so the samples share the running sweep number k (0, 1, ...) and sweep k lives
+    in ring slot k % R.  The frame of sweep k reads sweeps k-S+1 .. k; R >= S + inflight - 1 keeps the slot that sweep k
+    overwrites (that of sweep k-R) out of the reach of the inflight-1 frames that may still run (FrameStream, "Ordering")."""
+
+    def __init__(self, B, S, R, sweep_cap, ndim, inflight=1):
+        B, S, R = int(B), int(S), int(R)
+        if not 1 <= S <= MAX_SWEEPS:
+            raise ValueError("sweeps must be 1..%d, got %d" % (MAX_SWEEPS, S))
+        if int(sweep_cap) < 1:
+            raise ValueError("sweep_cap (the largest sweep the stream accepts) must be >= 1")
+        assert R >= S + int(inflight) - 1, "a ring of %d slots is overwritten under frames in flight" % R
+        self.B, self.S, self.R, self.sweep_cap, self.ndim = B, S, R, int(sweep_cap), int(ndim)
+        self.k = 0                                      # sweeps written so far
+        self.hist = [[] for _ in range(B)]              # per sample, newest first: (k, pose, time, points) of its sweeps
+
+    def plan(self, clouds, sweeps):
+        B, S = self.B, self.S
+        if sweeps is None:
+            raise ValueError("a stream with sweeps needs submit(clouds, sweeps=[dict(pose=, time=), ...]), one per cloud")
+        if len(clouds) != B:
+            raise ValueError("a batch of %d clouds for a stream of batch_size %d" % (len(clouds), B))
+        if len(sweeps) != B:
+            raise ValueError("%d sweep descriptions for a stream of batch_size %d" % (len(sweeps), B))
+        d = dict(k=self.k, write=self.k % self.R, slot=np.full((B, S), -1, np.int32), count=np.zeros((B, S), np.int32),
+                 xform=np.zeros((B, S), np.int32), T=np.zeros((B, S, 3, 4)), dt=np.zeros((B, S), np.float32), hist=[])
+        d["T"][:, :, :, :3] = np.eye(3)
+        for b, (pts, sw) in enumerate(zip(clouds, sweeps)):
+            if pts.ndim != 2 or pts.shape[1] != self.ndim:
+                raise ValueError("cloud %d has shape %s, expected [N, %d]" % (b, tuple(pts.shape), self.ndim))
+            if pts.shape[0] > self.sweep_cap:           # never detect on a silently truncated sweep
+                raise ValueError("cloud %d has %d points, the stream was sized for %d (sweep_cap)"
+                                 % (b, pts.shape[0], self.sweep_cap))
+            if not isinstance(sw, dict) or sw.get("pose") is None or sw.get("time") is None:
+                raise ValueError("sweep %d: a dict with `pose` and `time` is needed" % b)
+            pose = np.array(sw["pose"], dtype=np.float64)
+            if pose.shape != (4, 4) or not np.isfinite(pose).all():
+                raise ValueError("sweep %d: pose must be a finite 4x4 matrix" % b)
+            time = float(sw["time"])
+            if not np.isfinite(time):
+                raise ValueError("sweep %d: time must be finite" % b)
+            past = [] if sw.get("first", False) else self.hist[b][:S - 1]
+            d["slot"][b, 0], d["count"][b, 0] = d["write"], int(pts.shape[0])
+            for s, (k, pose_j, time_j, n_j) in enumerate(past, 1):
+                d["slot"][b, s], d["count"][b, s], d["xform"][b, s] = k % self.R, n_j, 1
+                d["T"][b, s] = sweep_transform(pose, pose_j)
+                d["dt"][b, s] = np.float32(time - time_j)
+            d["hist"].append([(self.k, pose, time, int(pts.shape[0]))] + past)
+        d["reads"] = sorted({int(v) for v in d["slot"][:, 1:].ravel() if v >= 0})
+        return d
+
+    def commit(self, d):
+        assert d["k"] == self.k
+        self.k += 1
+        self.hist = [h[:max(self.S - 1, 0)] for h in d["hist"]]
 
 
 class FrameStatusError(RuntimeError):
@@ -280,7 +408,8 @@ class FrameRing:
 
         stage(seq, clouds)   check and queue the inputs of one frame (ValueError for inputs it cannot take: nothing queued);
                              called as stage(seq, clouds, frustums) when submit() was given frustums, and only then;
-                             with calibs=<calibs> as a keyword when submit() was given calibs, and only then
+                             with calibs=<calibs> as a keyword when submit() was given calibs, and only then;
+                             with sweeps=<sweeps> as a keyword when submit() was given sweeps, and only then
         launch()             queue the frame and the copy of its record
         ready() / wait()     has the record arrived / block until it has
         record()             the arrived record, valid until the next stage()
@@ -315,7 +444,7 @@ class FrameRing:
                 recover()
         self.busy[i] = None
 
-    def submit(self, clouds, frustums=None, calibs=None):
+    def submit(self, clouds, frustums=None, calibs=None, sweeps=None):
         if self.closed:
             raise RuntimeError("FrameStream is closed")
         t = self.next_ticket
@@ -324,6 +453,8 @@ class FrameRing:
             self._harvest(i)
         args = (clouds,) if frustums is None else (clouds, frustums)
         kw = {} if calibs is None else dict(calibs=calibs)
+        if sweeps is not None:
+            kw["sweeps"] = sweeps
         self.slots[i].stage(t & _SEQ_MASK, *args, **kw)    # a ValueError leaves the ticket unused and the slot free
         self.slots[i].launch()
         self.busy[i] = t
@@ -356,7 +487,8 @@ class FrameRing:
     def map(self, batches):
         """(ticket, result) per batch of `batches`, in order, with at most len(slots) frames submitted and not yet yielded.
         A batch is a list of clouds, or the tuple (clouds, frustums) for a stream with raw_cap, or the tuple
-        (clouds, frustums-or-None, calibs) for a stream with annos."""
+        (clouds, frustums-or-None, calibs) for a stream with annos, or the tuple
+        (clouds, frustums-or-None, calibs-or-None, sweeps) for a stream with sweeps."""
         pending = deque()
         try:
             batches = iter(batches)
@@ -368,7 +500,7 @@ class FrameRing:
                     clouds = next(batches)
                 except StopIteration:
                     break
-                if isinstance(clouds, tuple):           # (clouds, frustums[, calibs]): a raw / annos stream's batch
+                if isinstance(clouds, tuple):           # (clouds, frustums[, calibs[, sweeps]]): a raw / annos / sweeps batch
                     pending.append(self.submit(*clouds))
                 else:
                     pending.append(self.submit(clouds))
@@ -397,35 +529,63 @@ class _PlanSlot:
     of the plan's staging block (`stage_layout`: planes with raw_cap, calibration with annos, seq, counts), pinned clouds
     [B x points_cap x ndim f32], a pinned record buffer and the event behind the record's copy.
     With raw_cap the frame crops: the pinned clouds are [B x raw_cap x ndim f32], they go to plan.raw_in and the plan's
-    first nodes cut them down to points_cap rows of plan.pts_in.  With annos the record is layout version 2."""
+    first nodes cut them down to points_cap rows of plan.pts_in.  With annos the record is layout version 2.
+    With `sweeps` -- dict(book=<SweepBook>, ring=<[B,R,sweep_cap,ndim] f32 device>, events=<one per ring slot>,
+    time_feature=), shared by the stream's slots -- `ndim` is the width of a submitted sweep, the pinned clouds are
+    [B x sweep_cap x ndim f32] and go into the ring slot the book names; the plan's first node merges the ring slots of
+    the frame's descriptors into plan.pts_in (ndim + time_feature columns)."""
 
-    def __init__(self, plan, points_cap, ndim, raw_cap=None, annos=False):
+    def __init__(self, plan, points_cap, ndim, raw_cap=None, annos=False, sweeps=None):
         import torch
         self.torch, self.plan = torch, plan
         dev, B = plan.dev, plan.B
         self.stream = torch.cuda.Stream(device=dev)
+        self.sw = sweeps
+        kw = dict(annos=True) if annos else {}
+        S, ndim_plan = 0, ndim
+        if sweeps is not None:
+            S, tf = sweeps["book"].S, bool(sweeps["time_feature"])
+            kw["sweeps"] = dict(ring=sweeps["ring"], S=S, sweep_cap=sweeps["book"].sweep_cap, time_feature=tf)
+            ndim_plan = int(ndim) + (1 if tf else 0)
         with torch.cuda.stream(self.stream):
-            plan.capture(points_cap, ndim=ndim, seal=True, raw_cap=raw_cap, **(dict(annos=True) if annos else {}))
+            plan.capture(points_cap, ndim=ndim_plan, seal=True, raw_cap=raw_cap, **kw)
         self.stream.synchronize()
         self.cap, self.ndim = int(points_cap), int(ndim)
         self.raw_cap = None if raw_cap is None else int(raw_cap)
         self.annos = bool(annos)
-        L = stage_layout(B, self.raw_cap is not None, self.annos, seal=True)
+        L = stage_layout(B, self.raw_cap is not None, self.annos, seal=True, **(dict(sweeps=S) if S else {}))
         self.pin_block = torch.zeros(L["total"], dtype=torch.uint8).pin_memory()     # the host side of plan._stage_block
         self.np_stage = stage_views(self.pin_block.numpy(), B, L)
         self.dev_pts, rows = (plan.pts_in, self.cap) if self.raw_cap is None else (plan.raw_in, self.raw_cap)
+        if S:
+            self.dev_pts, rows = None, sweeps["book"].sweep_cap      # the ring slot of the frame's sweep, chosen per frame
         self.pin_pts = torch.zeros(B, rows, self.ndim, dtype=torch.float32).pin_memory()
         self.pin_rec = torch.zeros(plan.record.numel(), dtype=torch.uint8).pin_memory()
         self.np_pts, self.np_rec = self.pin_pts.numpy(), self.pin_rec.numpy()
         self.event = torch.cuda.Event()
         self.feed = torch.cuda.Event()          # orders device-tensor clouds (produced on the caller's stream) before their copy
 
-    def stage(self, seq, clouds, frustums=None, calibs=None):
+    def stage(self, seq, clouds, frustums=None, calibs=None, sweeps=None):
         torch, plan = self.torch, self.plan
-        checked = check_frame_inputs(clouds, frustums, plan.B, self.ndim, self.cap, self.raw_cap, calibs,
-                                     self.annos)                                             # nothing is queued before this
         view = self.np_stage
-        planes, calib = checked if self.annos else (checked, None)
+        if self.sw is None:
+            if sweeps is not None:
+                raise ValueError("sweeps given to a stream built without sweeps= (its clouds are taken as they are)")
+            checked = check_frame_inputs(clouds, frustums, plan.B, self.ndim, self.cap, self.raw_cap, calibs,
+                                         self.annos)                                         # nothing is queued before this
+            planes, calib = checked if self.annos else (checked, None)
+            dev_pts = self.dev_pts
+        else:
+            if frustums is not None:
+                raise ValueError("frustums given to a stream with sweeps (merged clouds are not cropped)")
+            book = self.sw["book"]
+            d = book.plan(clouds, sweeps)                                                    # nothing is queued before this,
+            planes, calib = None, _check_calibs(calibs, None, plan.B, self.annos)            # and the book is unchanged
+            assert (d["k"] + 1) & _SEQ_MASK == seq      # ticket t carries sweep t - 1: frame t - inflight, the last reader of
+            book.commit(d)                              # the ring slot written now, ran on this slot's stream
+            for key in ("slot", "count", "xform", "T", "dt"):
+                view["sweep_" + key][...] = d[key]
+            dev_pts = [self.sw["ring"][b, d["write"]] for b in range(plan.B)]
         if planes is not None:
             view["planes"][...] = planes
         if calib is not None:
@@ -442,13 +602,18 @@ class _PlanSlot:
                 if n == 0:
                     continue
                 if on_dev[b]:
-                    self.dev_pts[b][:n].copy_(pts, non_blocking=True)
+                    dev_pts[b][:n].copy_(pts, non_blocking=True)
                     pts.record_stream(self.stream)      # the caller may drop the cloud now: its memory is not handed out
                                                         # again before this copy has run
                 else:
                     self.np_pts[b, :n] = pts.numpy() if torch.is_tensor(pts) else pts
-                    self.dev_pts[b][:n].copy_(self.pin_pts[b, :n], non_blocking=True)
+                    dev_pts[b][:n].copy_(self.pin_pts[b, :n], non_blocking=True)
             plan._stage_block.copy_(self.pin_block, non_blocking=True)
+        if self.sw is not None:
+            events = self.sw["events"]
+            events[d["write"]].record(self.stream)      # the sweep is in the ring for the frames that read it later ...
+            for r in d["reads"]:                        # ... and this frame reads sweeps other slots' streams uploaded
+                self.stream.wait_event(events[r])
 
     def launch(self):
         torch = self.torch
@@ -505,14 +670,47 @@ class FrameStream:
     non-positive image size, and calibs given to a stream without annos raise ValueError at submit, before anything is
     queued.  A frame whose status word is not zero raises plan.results()'s
     RuntimeError from ITS collect(); a record that is not the ticket's own raises RuntimeError("stale frame record").
-    `plans` are the InferencePlans (for tools); plan_kwargs go to InferencePlan (precision, sparse_precision, ...)."""
+    `plans` are the InferencePlans (for tools); plan_kwargs go to InferencePlan (precision, sparse_precision, ...).
+
+    Multi-sweep clouds: FrameStream(..., sweeps=S, sweep_cap=N, time_feature=True) detects on the current sweep plus the up
+    to S-1 sweeps before it, each moved into the current sensor frame by the ego pose (include/sassd.h "Multi-sweep merge",
+    one kernel per sample in front of the voxelizer).  `ndim` is then the width of a SUBMITTED sweep; the detector reads
+    ndim + 1 columns with time_feature (the last one the time lag in seconds, 0 for the current sweep).  Each sample index
+    is its own sensor sequence.  submit(clouds, sweeps=[dict(pose=<4x4 f64 sensor-to-world>, time=<seconds>,
+    first=<bool, default False>), ...]) takes the NEW sweep of every sample only, [n <= sweep_cap, ndim]: it crosses the bus
+    once, into the stream's device ring [B, R, sweep_cap, ndim], R = S + inflight - 1, at slot k % R for the k-th submit, and
+    stays there while later frames read it.  The frame's descriptors list the current sweep first (copied bit for bit),
+    then the earlier sweeps of the sequence, newest first, with T = sweep_transform(pose_now, pose_then) and
+    dt = float32(time_now - time_then); first=True starts a new sequence for that sample.  points_cap bounds the MERGED
+    cloud: a frame above it raises FrameStatusError with SASSD_ST_POINT_OVERFLOW (16) from its collect(), and its sweep
+    stays in the ring for the frames after it.  Missing / miscounted sweeps, a pose that is not a finite 4x4 matrix, a
+    non-finite time, a cloud above sweep_cap or of another width, frustums given to such a stream, and sweeps= given to a
+    stream built without it raise ValueError at submit, before anything is queued and with the sequence unchanged.
+    sweeps excludes raw_cap; annos composes with it unchanged.
+    Ordering: a sweep is uploaded on the stream of the slot whose frame brings it, and an event per ring slot is recorded
+    behind the upload.  (1) read after write: before its graph is launched, a frame's stream waits on the events of the
+    earlier sweeps it reads -- other slots' streams uploaded them.  (2) write after read: sweep k overwrites the ring slot
+    of sweep k - R; the last frame that read that one is the frame of sweep k - R + S - 1 = k - inflight, ticket
+    t - inflight, which ran on this same slot and stream, so stream order covers it; the frames that may still run on the
+    other streams, tickets t - inflight + 1 .. t - 1, read no sweep older than k - R + 1.  This holds because every ticket
+    writes exactly one sweep (a refused submit uses neither) -- the slot asserts it."""
 
     def __init__(self, state_dict, inflight=3, points_cap=None, batch_size=1, anchors=None, device=None, ndim=4,
-                 raw_cap=None, annos=False, **plan_kwargs):
+                 raw_cap=None, annos=False, sweeps=None, sweep_cap=None, time_feature=True, **plan_kwargs):
         from .pipeline import InferencePlan, input_features_of
         cin = input_features_of(state_dict)
-        if int(ndim) < cin:
-            raise ValueError("the detector reads %d features per point: FrameStream(ndim=%d) is too narrow" % (cin, int(ndim)))
+        if sweeps is not None:
+            if not 1 <= int(sweeps) <= MAX_SWEEPS:
+                raise ValueError("sweeps must be 1..%d, got %d" % (MAX_SWEEPS, int(sweeps)))
+            if raw_cap is not None:
+                raise ValueError("sweeps and raw_cap exclude each other: merged clouds are not cropped")
+            if sweep_cap is None or int(sweep_cap) < 1:
+                raise ValueError("sweep_cap (the largest sweep the stream accepts) is required with sweeps")
+            if int(ndim) < 3:
+                raise ValueError("a sweep has at least x, y, z: FrameStream(ndim=%d)" % int(ndim))
+        ndim_plan = int(ndim) + (1 if sweeps is not None and time_feature else 0)
+        if ndim_plan < cin:
+            raise ValueError("the detector reads %d features per point: FrameStream(ndim=%d) is too narrow" % (cin, ndim_plan))
         inflight = int(inflight)
         if not 1 <= inflight <= MAX_INFLIGHT:
             raise ValueError("inflight must be 1..%d, got %d" % (MAX_INFLIGHT, inflight))
@@ -528,10 +726,22 @@ class FrameStream:
         self.plans = [InferencePlan(state_dict, batch_size=batch_size, anchors=anchors, device=device,
                                     overlap=inflight == 1, **plan_kwargs) for _ in range(inflight)]
         B, capD = self.plans[0].B, self.plans[0].capD
-        self._slots = [_PlanSlot(p, self.points_cap, ndim, self.raw_cap, self.annos) for p in self.plans]
+        self.sweeps = None if sweeps is None else int(sweeps)
+        extra = {}
+        if self.sweeps is not None:
+            import torch
+            R = self.sweeps + inflight - 1              # class docstring, "Ordering"
+            self.sweep_cap, self.time_feature = int(sweep_cap), bool(time_feature)
+            self.sweep_ring = torch.zeros(B, R, self.sweep_cap, int(ndim), dtype=torch.float32, device=self.plans[0].dev)
+            self._book = SweepBook(B, self.sweeps, R, self.sweep_cap, ndim, inflight)
+            extra["sweeps"] = dict(book=self._book, ring=self.sweep_ring, time_feature=self.time_feature,
+                                   events=[torch.cuda.Event() for _ in range(R)])
+        self._slots = [_PlanSlot(p, self.points_cap, ndim, self.raw_cap, self.annos, **extra) for p in self.plans]
         self._ring = FrameRing(self._slots, lambda rec, seq: decode_record(rec, B, capD, seq, self.annos))
 
-    def submit(self, clouds, frustums=None, calibs=None):
+    def submit(self, clouds, frustums=None, calibs=None, sweeps=None):
+        if sweeps is not None:
+            return self._ring.submit(clouds, frustums, calibs, sweeps=sweeps)
         return self._ring.submit(clouds, frustums, calibs)
 
     def collect(self, ticket):
