@@ -294,8 +294,9 @@ __global__ void __launch_bounds__(256) rpn_loss_sum_kernel(const float *__restri
 // ---------------------------------------------------------------------------------------------------------------------
 // Guided-anchor selection of the training step (ssd_rotate_head.py:316-388: anchors inside the anchor mask whose best
 // class score exceeds train_cfg.rpn.anchor_thr), without the host round trip of a boolean compaction: ascending
-// anchor indices of the selected anchors land in sel[b][0 .. cnt[b]) of a FIXED-capacity buffer (the rest stays 0) and
-// the count stays on the device, so the decode / PSWarp / loss that follow run on padded tensors with a device count.
+// anchor indices of the selected anchors land in sel[b][0 .. cnt[b]) of a FIXED-capacity buffer (the rest is padded with
+// sel[b][p] = p) and the count stays on the device, so the decode / PSWarp / loss that follow run on padded tensors with
+// a device count.
 struct GuidedArgs {
     const float *cls;          // [B,A,NC] logits
     const uint8_t *mask;       // [B,A] or null
