@@ -7,7 +7,8 @@ checkpoint's torch optimizer state.
 The trajectory bar is the one of tests/test_gpu_optim.py: every parameter within 2e-6 * max(1, |ref|max) after every step.
 The reference's own fp32 run sits 1.6e-7 .. 3.7e-7 from its float64 run of the same steps (`<pair>/fp64_dist` in the
 golden file), so the bar leaves about 5x room; should a regenerated golden file ever record a distance above 1e-6 for a
-pair, that pair's bar is twice that distance (_bar)."""
+pair, that pair's bar is twice that distance (_bar).  test_kernel_edges also holds sassd_adam_step, the kernel of the default
+'adam_onecycle' type, to its rule."""
 import numpy as np
 import pytest
 import torch
@@ -103,6 +104,19 @@ def adam_l2_rule(p, g, m, v, sumsq, lr, b1, b2, eps, wd, step, max_norm, grad_sc
             np.abs(_f(b2) * v) + (1 - _f(b2)) * gsum * gsum)
 
 
+def adam_rule(p, g, m, v, sumsq, lr, b1, b2, eps, wd, step, max_norm, grad_scale):
+    """include/sassd.h, sassd_adam_step ('adam_onecycle': decoupled decay, csrc/optim.hip adam_one<false>), in float64 ->
+    (p', m', v', |update|, the magnitudes m' and v' are summed from).  The decay scales the parameter, p *= 1 - wd * lr, and
+    never joins the gradient: the moments see the clipped gradient alone."""
+    gc = g * _coef(sumsq, max_norm, grad_scale)
+    p0 = p * (1 - _f(wd) * _f(lr))
+    m1 = _f(b1) * m + (1 - _f(b1)) * gc
+    v1 = _f(b2) * v + (1 - _f(b2)) * gc * gc
+    upd = (m1 / (1 - _f(b1) ** step)) / (np.sqrt(v1) / np.sqrt(1 - _f(b2) ** step) + _f(eps))
+    return (p0 - _f(lr) * upd, m1, v1, np.abs(upd), np.abs(_f(b1) * m) + (1 - _f(b1)) * np.abs(gc),
+            np.abs(_f(b2) * v) + (1 - _f(b2)) * gc * gc)
+
+
 EDGE_N = (1, 3, 4, 5, 1023, 2_097_159)     # the last: one float4 beyond the 2048 x 256 x 4 grid -> a second stride iteration + a 3-element tail
 PAD = 9                                     # elements past n in every buffer: they must come back untouched
 
@@ -131,13 +145,15 @@ def _check(tag, got, want, bound, n):
 
 
 @pytest.mark.parametrize("n", EDGE_N)
-@pytest.mark.parametrize("kernel", ["sgd", "adam_l2"])
+@pytest.mark.parametrize("kernel", ["sgd", "adam_l2", "adam"])
 def test_kernel_edges(dev, kernel, n):
     """One step from random state against the documented rule in float64 (scalars as the fp32 values the ABI receives, the
     square sum as the device holds it).  Parameter bar: |err| <= 4 eps (|p| + lr |update|): the result is a handful of
     correctly rounded fp32 operations on the update and one subtraction from p (see _buffers for the state this holds on).
     The momentum buffer and the moments are sums of products that may cancel: 4 eps of the summed magnitudes of their
-    operands, |momentum buf| + |g'| + |wd p|; |beta1 m| + (1 - beta1)(|g'| + |wd p|); beta2 v + (1 - beta2)(|g'| + |wd p|)^2."""
+    operands, |momentum buf| + |g'| + |wd p|; |beta1 m| + (1 - beta1)(|g'| + |wd p|); beta2 v + (1 - beta2)(|g'| + |wd p|)^2.
+    "adam" is sassd_adam_step, the default OneCycle optimizer's kernel (decoupled decay): the same bars, without the wd p terms
+    in its moments (the decay scales the parameter: one more rounding of p, inside 4 eps |p|)."""
     lr, worst = 0.01, 0.0
     cases = [(clip, wd, mom) for clip in (False, True) for wd in (0.0, 0.01) for mom in ((0.9, 0.0) if kernel == "sgd" else (0.9,))]
     for ci, (clip, wd, mom) in enumerate(cases):
@@ -159,9 +175,9 @@ def test_kernel_edges(dev, kernel, n):
             assert torch.equal(t["s1"], before["s1"])
         else:
             step = 1 + ci
-            K.adam_l2_step(p, g, s0, s1, sumsq, lr, 0.9, 0.999, 1e-8, wd, step, max_norm, 0.5)
-            p1, m1, v1, upd, msum, vsum = adam_l2_rule(h["p"], h["g"], h["s0"], h["s1"], ssq, lr, 0.9, 0.999, 1e-8, wd, step,
-                                                 max_norm, 0.5)
+            step_fn, rule = (K.adam_l2_step, adam_l2_rule) if kernel == "adam_l2" else (K.adam_step, adam_rule)
+            step_fn(p, g, s0, s1, sumsq, lr, 0.9, 0.999, 1e-8, wd, step, max_norm, 0.5)
+            p1, m1, v1, upd, msum, vsum = rule(h["p"], h["g"], h["s0"], h["s1"], ssq, lr, 0.9, 0.999, 1e-8, wd, step, max_norm, 0.5)
             worst = max(worst, _check(tag + ("exp_avg",), t["s0"], m1, 4 * EPS * msum, n))
             worst = max(worst, _check(tag + ("exp_avg_sq",), t["s1"], v1, 4 * EPS * vsum, n))
         worst = max(worst, _check(tag + ("param",), t["p"], p1, 4 * EPS * (np.abs(h["p"]) + _f(lr) * upd), n))
