@@ -159,7 +159,11 @@ __global__ void __launch_bounds__(256) bn_finalize_kernel(BnApplyArgs P)
     if (threadIdx.x == 0) {
         double mean = ss / P.n;
         double var = qq / P.n - mean * mean;
-        if (mean * mean > 1024.0 * var) {                // the raw form cancels: see bn_stats_kernel
+        // the raw form cancels: see bn_stats_kernel.  Up to 1024 / C rows (one block, at most one row per thread) the re-based
+        // pair is EXACT -- a thread's residuals are zero and its shift is squared in double -- while the raw one carries the fp32
+        // rounding of every x^2 with no other row to average it out: two rows with mean^2 = 500 var lost 2e-5 of their variance
+        // (tests/test_gpu_backbone_grad_kernels.py, n = 2 .. 4).  No layer of a real frame is that short: their bits stay.
+        if (mean * mean > 1024.0 * var || P.n <= 1024 / P.C) {
             mean = s2 / P.n;
             var = q2 / P.n - mean * mean;
         }
