@@ -420,8 +420,9 @@ extern "C" int sassd_voxelize_dev(const float *points, int points_cap, const int
 extern "C" int sassd_voxel_mean(const float *voxels, const int32_t *num_points, int m, int max_points, int ndim,
                                 int nfeat, float *mean, void *stream_)
 {
-    if (m < 0 || !voxels || !num_points || !mean || nfeat > ndim) return SASSD_EINVAL;
-    if (m == 0) return SASSD_OK;
+    if (m < 0 || nfeat > ndim) return SASSD_EINVAL;
+    if (m == 0) return SASSD_OK;                             // (before the pointers: a tensor without rows has no address)
+    if (!voxels || !num_points || !mean) return SASSD_EINVAL;
     hipLaunchKernelGGL(voxel_mean_kernel, dim3(cdiv(m * nfeat, 256)), dim3(256), 0, (hipStream_t)stream_, voxels,
                        num_points, m, max_points, ndim, nfeat, mean);
     return sassd_launch_status();
