@@ -913,6 +913,18 @@ int sassd_points_global_transform(float *points, int n, int stride, int flip, fl
 int sassd_paste_objects(const float *db_points, const int64_t *src_start, const int64_t *out_start, int n_obj,
                         int64_t n_out, const double *shift, const double *lower, float *out, void *stream);
 
+/* The same gather for a database of `ndim` floats per point, ndim 3..8 (clouds with a time column, extra returns, ...):
+ *   db_points [P,ndim] f32 and out [n_out,ndim] f32, both dense (row stride = ndim floats); every other argument as above.
+ * Columns 0..2 are (float)((double)src + shift[k][c]), and column 2 is rounded a second time as
+ * (float)((double)z - lower[k]) when `lower` is given -- the arithmetic of sassd_paste_objects; columns 3..ndim-1 are
+ * copied bit for bit (NaN payloads, -0.0 and denormals included).  At ndim == 4 the output bytes are those of
+ * sassd_paste_objects.  An object of zero points repeats its out_start; row r belongs to the largest k with
+ * out_start[k] <= r.  The caller guarantees src_start[k] + count_k <= P.
+ * Returns SASSD_EINVAL for a negative count, ndim outside 3..8 or a missing array, SASSD_OK without a launch when
+ * n_obj == 0 or n_out == 0 -- all decided before anything is launched. */
+int sassd_paste_objects_nd(const float *db_points, int ndim, const int64_t *src_start, const int64_t *out_start,
+                           int n_obj, int64_t n_out, const double *shift, const double *lower, float *out, void *stream);
+
 /* HOST functions (no device memory, no stream): the sequential O(boxes^2 x tries) decisions.
  * `box_collision_test(boxes, qboxes)` geometry.py:593-672: boxes [n,4,2], qboxes [k,4,2] corner arrays (float64 when
  * is_f64, else float32) -> out [n,k] u8; edge crossings and full containment both count (numba evaluates the

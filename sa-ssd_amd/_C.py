@@ -177,6 +177,7 @@ _SIGS = {
     "sassd_points_transform": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
     "sassd_points_global_transform": (_I, [_P, _I, _I, _I, _F, _F, _F, _P]),
     "sassd_paste_objects": (_I, [_P, _P, _P, _I, C.c_int64, _P, _P, _P, _P]),
+    "sassd_paste_objects_nd": (_I, [_P, _I, _P, _P, _I, C.c_int64, _P, _P, _P, _P]),
     "sassd_box_collision_test": (_I, [_P, _I, _P, _I, _I, _P]),
     "sassd_noise_per_box": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "sassd_bn_relu_workspace_bytes": (_SZ, [_I]),

@@ -51,10 +51,11 @@ def _boxes_lidar(info, num_obj):
     return G.box_camera_to_lidar(cam, info['calib/R0_rect'], info['calib/Tr_velo_to_cam'])
 
 
-def _calculate_num_points_in_gt(data_path, infos, relative_path, remove_outside=True, num_features=4, device=None):
+def _calculate_num_points_in_gt(data_path, infos, relative_path, remove_outside=True, num_features=None, device=None):
+    """`num_features` None: each frame's own width, info['pointcloud_num_features']"""
     for info in infos:
         v_path = pathlib.Path(data_path) / info["velodyne_path"] if relative_path else info["velodyne_path"]
-        pts = _load_points(v_path, num_features, device)
+        pts = _load_points(v_path, info.get('pointcloud_num_features', 4) if num_features is None else num_features, device)
         if remove_outside:
             pts = _in_image(pts, info)
         annos = info['annos']
@@ -65,18 +66,21 @@ def _calculate_num_points_in_gt(data_path, infos, relative_path, remove_outside=
         annos["num_points_in_gt"] = np.concatenate([counts, -np.ones([ignored])]).astype(np.int32)
 
 
-def create_kitti_info_file(data_path, save_path=None, relative_path=True, device=None):
+def create_kitti_info_file(data_path, save_path=None, relative_path=True, device=None, num_features=4):
+    """`num_features`: floats per point of the tree's velodyne files (3..8, xyz first); recorded in every info as
+    'pointcloud_num_features', which the other two steps read."""
     sets = {k: _read_imageset_file(str(pathlib.Path(data_path) / "ImageSets" / (k + ".txt")))
             for k in ("train", "val", "test")}
     save_path = pathlib.Path(data_path if save_path is None else save_path)
     infos = {}
     for k in ("train", "val"):
         infos[k] = kitti.get_kitti_image_info(data_path, training=True, velodyne=True, calib=True, image_ids=sets[k],
-                                              relative_path=relative_path)
+                                              relative_path=relative_path, num_features=num_features)
         _calculate_num_points_in_gt(data_path, infos[k], relative_path, device=device)
     infos["trainval"] = infos["train"] + infos["val"]
     infos["test"] = kitti.get_kitti_image_info(data_path, training=False, label_info=False, velodyne=True, calib=True,
-                                               image_ids=sets["test"], relative_path=relative_path)
+                                               image_ids=sets["test"], relative_path=relative_path,
+                                               num_features=num_features)
     for k, v in infos.items():
         with open(save_path / ('kitti_infos_%s.pkl' % k), 'wb') as f:
             pickle.dump(v, f)
@@ -88,7 +92,7 @@ def _create_reduced_point_cloud(data_path, info_path, save_path=None, back=False
         kitti_infos = pickle.load(f)
     for info in kitti_infos:
         v_path = pathlib.Path(data_path) / info['velodyne_path']
-        pts = _load_points(v_path, 4, device)
+        pts = _load_points(v_path, info.get('pointcloud_num_features', 4), device)
         if back:
             pts[:, 0] = -pts[:, 0]
         pts = _in_image(pts, info)
@@ -126,7 +130,8 @@ def create_groundtruth_database(data_path, info_path=None, used_classes=None, da
     group_counter = 0
     for info in kitti_infos:
         v_path = str(root / info['velodyne_path']) if relative_path else info['velodyne_path']
-        pts = _load_points(v_path, info.get('pointcloud_num_features', 4), device)
+        width = info.get('pointcloud_num_features', 4)
+        pts = _load_points(v_path, width, device)
         if not lidar_only:
             pts = _in_image(pts, info)
         annos = info["annos"]
@@ -154,6 +159,8 @@ def create_groundtruth_database(data_path, info_path=None, used_classes=None, da
                     group_dict[group_ids[i]] = group_counter
                     group_counter += 1
                 db_info["group_id"] = group_dict[group_ids[i]]
+                if width != 4:                                              # a 4-wide database keeps the reference's keys
+                    db_info["num_point_features"] = width
                 if "score" in annos:
                     db_info["score"] = annos["score"][i]
                 all_db_infos[names[i]].append(db_info)

@@ -7,7 +7,8 @@
 //   global_transform      random_flip + global_rotation + global_scaling (points)   point_augmentor.py:279-303
 //   paste_objects         the sampled ground-truth objects' points   point_augmentor.py:232-242
 // The O(boxes^2 x tries) sequential choices (collision tests, noise selection) are host code in augment_host.hip.
-// All four kernels are HBM streams of 16 B per point (+ m mask bytes); the arithmetic lives in augment_core.h.
+//   paste_objects_nd      the same at 3..8 floats per point: xyz moved, the other columns copied
+// All of them are HBM streams of one row per point (+ m mask bytes); the arithmetic lives in augment_core.h.
 #include "augment_core.h"
 #include "common.h"
 
@@ -68,6 +69,34 @@ __global__ void __launch_bounds__(256) paste_objects_kernel(const float *__restr
     const float *src = db_points + (src_start[k] + (r - out_start[k])) * 4;
     paste_point(src, out + r * 4, shift + 3 * k, lower ? lower + k : nullptr);
 }
+
+// The same gather for rows of W = 3..8 floats.  Rows of 12, 20, 28 bytes are not 16-byte aligned, so a thread per row would
+// issue W strided dword accesses per wave; here a thread owns ONE float of the output, lane i of a wave reads and writes
+// dword i of a contiguous 256-byte run whatever W is.  W is a template argument: e / W is a multiply and a shift.
+template <int W>
+__global__ void __launch_bounds__(256) paste_objects_nd_kernel(const float *__restrict__ db_points,
+                                                               const int64_t *__restrict__ src_start,
+                                                               const int64_t *__restrict__ out_start, int n_obj,
+                                                               int64_t n_elem, const double *__restrict__ shift,
+                                                               const double *__restrict__ lower, float *__restrict__ out)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_elem) return;
+    const int64_t r = e / W;
+    const int c = (int)(e - r * W);
+    const int k = object_of_row(out_start, n_obj, r);
+    const float v = db_points[(src_start[k] + (r - out_start[k])) * W + c];
+    out[e] = paste_value_nd(v, c, shift + 3 * k, lower ? lower + k : nullptr);
+}
+
+template <int W>
+void launch_paste_nd(hipStream_t stream, const float *db_points, const int64_t *src_start, const int64_t *out_start,
+                     int n_obj, int64_t n_out, const double *shift, const double *lower, float *out)
+{
+    const int64_t n_elem = n_out * W;
+    hipLaunchKernelGGL(paste_objects_nd_kernel<W>, dim3((unsigned)((n_elem + 255) / 256)), dim3(256), 0, stream,
+                       db_points, src_start, out_start, n_obj, n_elem, shift, lower, out);
+}
 }  // namespace
 
 extern "C" int sassd_points_in_polytopes(const float *points, int n, int stride, const double *planes, int m,
@@ -113,5 +142,25 @@ extern "C" int sassd_paste_objects(const float *db_points, const int64_t *src_st
     if (!db_points || !src_start || !out_start || !shift || !out) return SASSD_EINVAL;
     hipLaunchKernelGGL(paste_objects_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, (hipStream_t)stream_,
                        db_points, src_start, out_start, n_obj, n_out, shift, lower, out);
+    return sassd_launch_status();
+}
+
+extern "C" int sassd_paste_objects_nd(const float *db_points, int ndim, const int64_t *src_start,
+                                      const int64_t *out_start, int n_obj, int64_t n_out, const double *shift,
+                                      const double *lower, float *out, void *stream_)
+{
+    if (n_obj < 0 || n_out < 0 || ndim < 3 || ndim > 8) return SASSD_EINVAL;
+    if (n_obj == 0 || n_out == 0) return SASSD_OK;
+    if (!db_points || !src_start || !out_start || !shift || !out) return SASSD_EINVAL;
+    if (n_out > (int64_t)0x7fffffff * (256 / 8)) return SASSD_EINVAL;       // the grid's x extent: n_out * ndim / 256 blocks
+    hipStream_t stream = (hipStream_t)stream_;
+    switch (ndim) {
+    case 3: launch_paste_nd<3>(stream, db_points, src_start, out_start, n_obj, n_out, shift, lower, out); break;
+    case 4: launch_paste_nd<4>(stream, db_points, src_start, out_start, n_obj, n_out, shift, lower, out); break;
+    case 5: launch_paste_nd<5>(stream, db_points, src_start, out_start, n_obj, n_out, shift, lower, out); break;
+    case 6: launch_paste_nd<6>(stream, db_points, src_start, out_start, n_obj, n_out, shift, lower, out); break;
+    case 7: launch_paste_nd<7>(stream, db_points, src_start, out_start, n_obj, n_out, shift, lower, out); break;
+    default: launch_paste_nd<8>(stream, db_points, src_start, out_start, n_obj, n_out, shift, lower, out); break;
+    }
     return sassd_launch_status();
 }

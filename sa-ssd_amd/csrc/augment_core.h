@@ -84,4 +84,21 @@ __host__ __device__ inline void paste_point(const float *src, float *dst, const 
     dst[3] = src[3];
 }
 
+// The same for a cloud of `ndim` (3..8) floats per point: x, y, z move exactly as in paste_point, every further column is
+// copied bit for bit (a float register move: NaN payloads, -0.0 and denormals survive).  paste_value_nd is column c of one
+// row -- what one thread of paste_objects_nd_kernel computes -- and paste_point_nd the whole row, for the CPU harness.
+__host__ __device__ inline float paste_value_nd(float v, int c, const double *shift, const double *lower)
+{
+    if (c >= 3) return v;
+    float m = (float)((double)v + shift[c]);
+    if (c == 2 && lower) m = (float)((double)m - *lower);
+    return m;
+}
+
+__host__ __device__ inline void paste_point_nd(const float *src, float *dst, int ndim, const double *shift,
+                                               const double *lower)
+{
+    for (int c = 0; c < ndim; ++c) dst[c] = paste_value_nd(src[c], c, shift, lower);
+}
+
 }  // namespace sassd_aug

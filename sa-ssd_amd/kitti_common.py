@@ -150,8 +150,12 @@ def project_rect_to_image(pts_rect, calib):
     return uvw[..., 0:2]
 
 
-def read_lidar(bin_path):
-    return np.fromfile(bin_path, dtype=np.float32).reshape(-1, 4)
+def read_lidar(bin_path, num_features=4):
+    """a sweep of `num_features` float32 per point (x, y, z first); a file of another width is refused, not misparsed"""
+    pts = np.fromfile(bin_path, dtype=np.float32)
+    if pts.size % num_features:
+        raise ValueError("%s holds %d floats, not a whole number of %d-feature points" % (bin_path, pts.size, num_features))
+    return pts.reshape(-1, num_features)
 
 
 # ---- boxes -------------------------------------------------------------------------------------------------------
@@ -272,15 +276,16 @@ def _calib_rows(path):
 
 
 def get_kitti_image_info(path, training=True, label_info=True, velodyne=False, calib=False, image_ids=7481,
-                         extend_matrix=True, num_worker=8, relative_path=True, with_imageshape=True):
-    """One dict per frame: image_idx, pointcloud_num_features, velodyne_path, img_path, img_shape, calib/P0..P3,
+                         extend_matrix=True, num_worker=8, relative_path=True, with_imageshape=True, num_features=4):
+    """One dict per frame: image_idx, pointcloud_num_features (= num_features, the floats per point of the velodyne
+    files), velodyne_path, img_path, img_shape, calib/P0..P3,
     calib/R0_rect, calib/Tr_velo_to_cam, calib/Tr_imu_to_velo (4x4 when extend_matrix), annos (+ difficulty)."""
     root = pathlib.Path(path)
     if not isinstance(image_ids, list):
         image_ids = list(range(image_ids))
     infos = []
     for idx in image_ids:
-        info = {'image_idx': idx, 'pointcloud_num_features': 4}
+        info = {'image_idx': idx, 'pointcloud_num_features': num_features}
         if velodyne:
             info['velodyne_path'] = get_velodyne_path(idx, path, training, relative_path)
         info['img_path'] = get_image_path(idx, path, training, relative_path)

@@ -58,7 +58,13 @@ class KittiLiDAR:
     def __init__(self, root, ann_file, img_prefix=None, img_norm_cfg=None, img_scale=(1242, 375), size_divisor=32,
                  proposal_file=None, flip_ratio=0.5, with_point=False, with_mask=False, with_label=True, with_plane=False,
                  class_names=('Car', 'Van'), augmentor=None, generator=None, anchor_generator=None,
-                 anchor_area_threshold=1, target_encoder=None, out_size_factor=2, test_mode=False, device=None):
+                 anchor_area_threshold=1, target_encoder=None, out_size_factor=2, test_mode=False, device=None,
+                 num_point_features=4):
+        """`num_point_features`: floats per point of the velodyne_reduced files (3..8, xyz first) -- the width the tree was
+        prepared at (create_data: num_features), of the augmentor's database and of the model's num_input_features."""
+        if not 3 <= int(num_point_features) <= 8:
+            raise ValueError("num_point_features is %s: clouds hold 3..8 floats per point" % (num_point_features,))
+        self.num_point_features = int(num_point_features)
         self.root = root
         self.img_scales = img_scale if isinstance(img_scale, list) else [img_scale]
         self.class_names = list(class_names)
@@ -107,7 +113,7 @@ class KittiLiDAR:
         return (h, w, 3)
 
     def load_frame(self, idx, with_label=True, lidar_prefix=None):
-        """Everything the files hold for sample idx: dict(sample_idx, img_shape, calib, points [N,4] f32 numpy,
+        """Everything the files hold for sample idx: dict(sample_idx, img_shape, calib, points [N,W] f32 numpy,
         gt_bboxes [G,7] f32 lidar frame, gt_types list, plane).  `lidar_prefix`: read the points from that directory
         instead of self.lidar_prefix (raw sweeps: runner.single_test(raw_prefix=...))."""
         sample_id = self.sample_ids[idx]
@@ -119,7 +125,8 @@ class KittiLiDAR:
                 boxes[:, :3] = project_rect_to_velo(boxes[:, :3], calib)      # camera -> lidar (kitti.py:152-154)
             out.update(gt_bboxes=boxes, gt_types=types)
         if self.with_point:
-            out['points'] = read_lidar(osp.join(lidar_prefix or self.lidar_prefix, '%06d.bin' % sample_id))
+            out['points'] = read_lidar(osp.join(lidar_prefix or self.lidar_prefix, '%06d.bin' % sample_id),
+                                       self.num_point_features)
         if self.with_plane:
             out['plane'] = get_road_plane(osp.join(self.plane_prefix, '%06d.txt' % sample_id))
         return out
@@ -181,8 +188,15 @@ class KittiLiDAR:
 
     def collate(self, samples, model=None):
         """list of prepare_*_img results -> kwargs of model(...): voxelization and anchor masks run here, on the device.
-        Train mode adds the sparse-conv rulebooks of the batch when `model` is given (sassd.train.device_batch)."""
+        Train mode adds the sparse-conv rulebooks of the batch when `model` is given (sassd.train.device_batch).  Clouds
+        narrower than the model's num_input_features are refused here, before anything is launched."""
         from . import train
+        want = getattr(getattr(model, "backbone", None), "num_input_features", None)    # SimpleVoxel reads that many columns
+        if want is not None:
+            for s in samples:
+                if s['points'].shape[1] < want:
+                    raise ValueError("the clouds hold %d features per point, the model's num_input_features is %d"
+                                     % (s['points'].shape[1], want))
         gen = self.generator
         an, bv = self._anchors_on_device()
         metas = [s['img_meta'] for s in samples]

@@ -3,8 +3,10 @@ mmdet/core/point_cloud/point_augmentor.py (`PointAugmentor`, `BatchSampler`; use
 re-designed for one MI355X per process instead of four numba DataLoader workers per GPU:
 
   * the ground-truth database (tools/create_data.py: kitti_dbinfos_train.pkl + gt_database/*.bin, a few hundred MB for
-    KITTI) is read ONCE and kept resident in HBM as one packed [P,4] array; pasting sampled objects is a gather kernel
-    (sassd_paste_objects), not `np.fromfile` per object per iteration (point_augmentor.py:232-242);
+    KITTI) is read ONCE and kept resident in HBM as one packed [P,W] array; pasting sampled objects is a gather kernel
+    (sassd_paste_objects at W = 4, sassd_paste_objects_nd at the other widths 3..8), not `np.fromfile` per object per
+    iteration (point_augmentor.py:232-242).  W is the database's own width (`num_point_features`); a cloud of another
+    width is refused.  x, y, z are moved, every further column travels with its point unchanged;
   * the frame's sweep is uploaded once; point-in-box masks (sassd_points_in_polytopes), the per-object move
     (sassd_points_transform) and flip + global rotation + global scaling fused in one pass
     (sassd_points_global_transform) run one thread per point and hand the cloud straight to the HIP voxelizer;
@@ -47,6 +49,15 @@ def _paste_objects(db, src_start, out_start, n_obj, n_out, shift, lower, out):
     with torch.cuda.device(out.device):
         _C.check(_C.lib().sassd_paste_objects(_ptr(db), _ptr(src_start), _ptr(out_start), n_obj, n_out, _ptr(shift),
                                               _ptr(lower), _ptr(out), _C.stream()), "sassd_paste_objects")
+
+
+def _paste_objects_nd(db, src_start, out_start, n_obj, n_out, shift, lower, out):
+    """the gather at the database's own width db.shape[1] (3..8)"""
+    _on_gpu(db, src_start, out_start, shift, lower, out)
+    with torch.cuda.device(out.device):
+        _C.check(_C.lib().sassd_paste_objects_nd(_ptr(db), db.shape[1], _ptr(src_start), _ptr(out_start), n_obj, n_out,
+                                                 _ptr(shift), _ptr(lower), _ptr(out), _C.stream()),
+                 "sassd_paste_objects_nd")
 
 
 def _points_transform(points, mask8, valid, centers, rot_sin, rot_cos, loc):
@@ -119,9 +130,22 @@ class BatchSampler:
 
 class PointAugmentor:
     def __init__(self, root_path, info_path, sample_classes, min_num_points, sample_max_num, removed_difficulties,
-                 gt_rot_range=None, global_rot_range=None, center_noise_std=None, scale_range=None, device=None):
+                 gt_rot_range=None, global_rot_range=None, center_noise_std=None, scale_range=None, device=None,
+                 num_point_features=None):
+        """`num_point_features`: floats per database point, 3..8; None takes it from the db infos' 'num_point_features'
+        key (create_data writes it for every width but 4) and is 4 without one."""
         with open(info_path, 'rb') as f:
             db_infos_all = pickle.load(f)
+        if num_point_features is None:
+            stated = {info["num_point_features"] for infos in db_infos_all.values() for info in infos
+                      if "num_point_features" in info}
+            if len(stated) > 1:
+                raise ValueError("%s states more than one num_point_features: %s" % (info_path, sorted(stated)))
+            num_point_features = stated.pop() if stated else 4
+        width = int(num_point_features)
+        if not 3 <= width <= 8:
+            raise ValueError("num_point_features is %d: the ground-truth database holds 3..8 floats per point" % width)
+        self.num_point_features = width
         if isinstance(min_num_points, int):
             min_num_points = [min_num_points] * len(sample_classes)
         self.root_path = root_path
@@ -130,12 +154,17 @@ class PointAugmentor:
             kept = [dict(info) for info in db_infos_all[cls]
                     if info["num_points_in_gt"] >= min_num_points[i] and info["difficulty"] not in removed_difficulties]
             for info in kept:                                    # read every object's points once
-                pts = np.fromfile(str(pathlib.Path(root_path) / info["path"]), dtype=np.float32).reshape([-1, 4])
+                path = str(pathlib.Path(root_path) / info["path"])
+                pts = np.fromfile(path, dtype=np.float32)
+                if pts.size != info["num_points_in_gt"] * width:
+                    raise ValueError("%s holds %d floats, not the %d points x %d features its db info states (expected "
+                                     "width %d)" % (path, pts.size, info["num_points_in_gt"], width, width))
+                pts = pts.reshape([-1, width])
                 info["_start"], info["_count"] = at, len(pts)
                 rows.append(pts)
                 at += len(pts)
             self._samplers.append(BatchSampler(kept, cls))
-        self._db_points = np.concatenate(rows, 0) if rows else np.zeros((0, 4), np.float32)
+        self._db_points = np.concatenate(rows, 0) if rows else np.zeros((0, width), np.float32)
         self._db_dev = None
         self.device = None if device is None else torch.device(device)
         self._sample_classes = sample_classes
@@ -157,8 +186,14 @@ class PointAugmentor:
             self._db_dev = torch.from_numpy(self._db_points).to(self._dev())
         return self._db_dev
 
+    def _check_width(self, points):
+        """A cloud of another width than the database's is refused on entry, before a random draw or a launch."""
+        if points.ndim != 2 or points.shape[1] != self.num_point_features:
+            raise ValueError("the cloud is %s: %s features per point, the ground-truth database has %d"
+                             % (list(points.shape), points.shape[1] if points.ndim == 2 else "?", self.num_point_features))
+
     def _points_in(self, points):
-        """-> (GPU tensor [N,4] f32, the numpy array to write back into or None)"""
+        """-> (GPU tensor [N,W] f32, the numpy array to write back into or None)"""
         if torch.is_tensor(points):
             return points, None
         return torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32)).to(self._dev()), points
@@ -219,26 +254,28 @@ class PointAugmentor:
         return sampled, boxes, mv_height
 
     def paste(self, sampled, mv_height=None):
-        """The sampled objects' points, gathered on the GPU from the resident database: [sum counts, 4] f32."""
+        """The sampled objects' points, gathered on the GPU from the resident database: [sum counts, W] f32."""
         dev = self._dev()
         counts = np.array([s["_count"] for s in sampled], dtype=np.int64)
         out_start = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         n_out = int(out_start[-1])
-        out = torch.empty((n_out, 4), dtype=torch.float32, device=dev)
+        width = self.num_point_features
+        out = torch.empty((n_out, width), dtype=torch.float32, device=dev)
         if n_out:
             t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
             src = t(np.array([s["_start"] for s in sampled], dtype=np.int64))
             shift = t(np.stack([s["box3d_lidar"][:3] for s in sampled]).astype(np.float64))
             lower = None if mv_height is None else t(np.asarray(mv_height, dtype=np.float64))
             ostart = t(out_start)
-            _paste_objects(self.database_on_device(), src, ostart, len(sampled), n_out, shift, lower, out)
+            gather = _paste_objects if width == 4 else _paste_objects_nd
+            gather(self.database_on_device(), src, ostart, len(sampled), n_out, shift, lower, out)
         return out
 
     def sample_all(self, gt_boxes, gt_types, road_planes=None, calib=None, as_numpy=True):
-        """-> (sampled_gt_boxes [S,7] f32, sampled_gt_types, sampled_points [P,4] f32)   (point_augmentor.py:191-247)"""
+        """-> (sampled_gt_boxes [S,7] f32, sampled_gt_types, sampled_points [P,W] f32)   (point_augmentor.py:191-247)"""
         sampled, boxes, mv_height = self.select_samples(gt_boxes, gt_types, road_planes, calib)
         if not sampled:
-            empty = np.empty((0, 4), dtype=np.float32)
+            empty = np.empty((0, self.num_point_features), dtype=np.float32)
             return np.empty((0, 7), dtype=np.float32), [], empty if as_numpy else torch.from_numpy(empty).to(self._dev())
         pts = self.paste(sampled, mv_height)
         return boxes.astype(np.float32), [s['name'] for s in sampled], pts.cpu().numpy() if as_numpy else pts
@@ -271,6 +308,8 @@ class PointAugmentor:
     def noise_per_object_(self, gt_boxes, points=None, valid_mask=None, num_try=100):
         """Moves every ground-truth box (and the points inside it) by the first of `num_try` random (shift, yaw) draws that
         does not make it collide with another box; in place on gt_boxes and points (point_augmentor.py:306-346)."""
+        if points is not None:
+            self._check_width(points)
         loc_t, rot_t, valid = self.draw_object_noise(gt_boxes, valid_mask, num_try)
         if points is not None:
             dev_pts, host = self._points_in(points)
@@ -287,6 +326,7 @@ class PointAugmentor:
         return self._points_out(dev_pts, host)
 
     def random_flip(self, gt_boxes, points, probability=0.5):
+        self._check_width(points)
         enable = np.random.choice([False, True], replace=False, p=[1 - probability, probability])
         if enable:
             gt_boxes[:, 1] = -gt_boxes[:, 1]
@@ -295,6 +335,7 @@ class PointAugmentor:
         return gt_boxes, points
 
     def global_rotation(self, gt_boxes, points):
+        self._check_width(points)
         angle = np.random.uniform(self._global_rot_range[0], self._global_rot_range[1])
         points = self._global(points, False, angle, 1.0)
         gt_boxes[:, :3] = G.rotation_points_single_angle(gt_boxes[:, :3], angle, axis=2)
@@ -302,6 +343,7 @@ class PointAugmentor:
         return gt_boxes, points
 
     def global_scaling(self, gt_boxes, points):
+        self._check_width(points)
         scale = np.random.uniform(self._min_scale, self._max_scale)
         points = self._global(points, False, 0.0, scale)
         gt_boxes[:, :6] *= scale
@@ -309,10 +351,11 @@ class PointAugmentor:
 
     # ---- the whole training-frame recipe, fused (mmdet/datasets/kitti.py:209-238) ---------------------------------------------
     def augment_frame(self, points, gt_boxes, gt_types, class_names, road_planes=None, calib=None, num_try=100):
-        """points [N,4] (numpy or GPU tensor), gt_boxes [G,7] f32 lidar, gt_types list -> (points on the GPU, gt_boxes,
+        """points [N,W] (numpy or GPU tensor), gt_boxes [G,7] f32 lidar, gt_types list -> (points on the GPU, gt_boxes,
         gt_types array, gt_labels): paste sampled objects, drop the scene points they cover, Van -> Car, keep
         `class_names`, per-object noise, flip, global rotation, global scaling -- the last three in ONE pass over the
         points.  Consumes numpy's global random stream in the reference's order."""
+        self._check_width(points)
         dev_pts, _ = self._points_in(points)
         sampled, s_boxes, mv_height = self.select_samples(gt_boxes, gt_types, road_planes, calib)
         if sampled:
