@@ -176,6 +176,53 @@ int sassd_merge_sweeps_dev(const float *ring, int R, int sweep_cap, int ndim_in,
                            int time_feature, float *out, int cap_out, int32_t *n_out_dev, int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Test-time augmentation: the detector runs on V views of every cloud inside ONE captured frame, and the candidates of
+ * the views are suppressed together.  Two kernels frame the unchanged detector, which runs an inner batch of b * V samples
+ * (inner sample s * V + v is view v of user sample s): sassd_tta_views_dev in front of the voxelizer, sassd_tta_pool
+ * between sassd_pswarp_sample and sassd_rescore_nms, which then runs with batch = b and capK = capP.  (The reference's
+ * BaseDetector.forward_test dispatches to an aug_test hook that its 3-D detector never implements.)
+ *
+ * CONTRACT
+ *   view       (flip, angle, scale): flip 0 / 1 (y -> -y), angle in radians, scale > 0.  A call takes V = 1..8 views as
+ *              HOST arrays read before it returns: flip [V] i32, rot_sin [V] = float32(sin(angle)), rot_cos [V] =
+ *              float32(cos(angle)), scale [V] = float32(scale) and, for the pool, angle [V] = float32(angle).  View 0 is the
+ *              identity: flip 0, rot_sin 0, rot_cos 1, scale 1 (angle 0).
+ *   forward    sassd_tta_views_dev: src [cap, ndim] f32 device and its device count *n_src_dev are view 0, as they are.
+ *              dst[v - 1] ([cap_dst, ndim] f32 device) and *n_dst_dev[v - 1], v = 1 .. V - 1 (HOST arrays of V - 1 device
+ *              pointers) receive view v: n = clamp(*n_src_dev, 0, cap) rows and the count n.  x, y, z of a row are
+ *              global_point of csrc/augment_core.h -- flip, then rotate, then scale; float32, every product and sum rounded
+ *              on its own (no fused multiply-add) -- and every further column is copied bit for bit.  Rows of a
+ *              destination at and beyond n are not written.  V == 1 launches nothing.
+ *   inverse    a candidate box (x, y, z, w, l, h, yaw) of view v >= 1 returns to the sensor frame by unview_box of
+ *              csrc/tta_core.h: float32, no fused multiply-add, each product, quotient and sum rounded on its own, in this
+ *              order: (1) the first six fields are divided by scale; (2) x = x' * c - y' * s, y = x' * s + y' * c,
+ *              yaw -= angle; (3) with flip: y = -y, yaw = -yaw + float32(pi).  Boxes of view 0 are copied bit for bit.
+ *   pool       sassd_tta_pool: guided [b * V, capK, 7] f32, logits [b * V, capK] f32, labels [b * V, capK] i32, counts
+ *              [b * V] i32 (the buffers of sassd_decode_filter / sassd_pswarp_sample at the inner batch) -> guided_p
+ *              [b, capP, 7], logits_p [b, capP], labels_p [b, capP], counts_p [b].  The pooled rows of a sample are
+ *              VIEW-MAJOR: view v contributes its first c_v = clamp(counts[s * V + v], 0, capK) rows in their order, boxes
+ *              through the inverse, logits and labels copied.  counts_p[s] = min(sum_v c_v, capP); rows at and beyond it
+ *              are not written.  (sassd_rescore_nms sorts stably: among equal scores the identity view wins.)
+ *   overflow   sum_v c_v > capP: the rows past capP are dropped and SASSD_ST_BOX_OVERFLOW is OR-ed into *status, which is
+ *              only ever OR-ed into.  A plan uses capP = min(V * capK, 4096), the most sassd_rescore_nms takes.
+ *   launches   one kernel each, no workspace: views (ceil(cap * ndim / 256), V - 1) workgroups, one thread per output
+ *              float; pool (ceil(capP / 256), b) workgroups, one thread per pooled row.  No host sync, no allocation, no
+ *              memset, no atomics but the OR into `status`, no workgroup waits for another.
+ *   errors     SASSD_EINVAL before any HIP call: V outside 1..8, ndim < 3, cap / batch / capK / capP < 1, capP > 4096, a
+ *              NULL or misaligned (4 bytes) pointer, a destination that is the source, a view 0 that is not the identity,
+ *              a flip that is not 0 / 1, a scale that is not positive and finite, a sine or cosine outside [-1, 1], an
+ *              angle that is not finite.  SASSD_ENOSPC: cap_dst < cap (a destination cannot hold the source); capP <
+ *              min(capK, 4096) (the pool cannot hold the identity view whole).
+ * ---------------------------------------------------------------------------------------------- */
+int sassd_tta_views_dev(const float *src, int cap, const int32_t *n_src_dev, int ndim, int V, const int32_t *flip,
+                        const float *rot_sin, const float *rot_cos, const float *scale, float *const *dst,
+                        int32_t *const *n_dst_dev, int cap_dst, void *stream);
+int sassd_tta_pool(const float *guided, const float *logits, const int32_t *labels, const int32_t *counts, int batch,
+                   int V, int capK, const int32_t *flip, const float *rot_sin, const float *rot_cos, const float *scale,
+                   const float *angle, float *guided_p, float *logits_p, int32_t *labels_p, int32_t *counts_p, int capP,
+                   int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * (a5) Rulebook build.  Replaces spconv v1.0 `get_indice_pairs` as invoked by SubMConv3d / SparseConv3d
  * (call sites mmdet/models/necks/cmn.py:147-173).  The rulebook is a gather table
  *   nbr[row_out, 27]  = input row feeding output row_out through kernel offset k=(kz*3+ky)*3+kx, or -1

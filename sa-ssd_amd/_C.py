@@ -46,6 +46,9 @@ _SIGS = {
     "sassd_crop_polytope_dev": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _SZ, _P]),
     # multi-sweep merge (include/sassd.h "Multi-sweep merge")
     "sassd_merge_sweeps_dev": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P]),
+    # test-time augmentation (include/sassd.h "Test-time augmentation")
+    "sassd_tta_views_dev": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "sassd_tta_pool": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
     "sassd_hash_bytes": (_SZ, [_I]),
     "sassd_hash_build": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P, _P]),
     "sassd_rulebook_subm": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P, _P]),

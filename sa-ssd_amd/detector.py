@@ -891,8 +891,15 @@ class SingleStageDetector(nn.Module):
         precision = kw.pop('precision', None) or ((self.test_cfg or {}).get('precision') or 'fp32')
         # test_cfg['sparse_precision'] (optional, top level): "fp32" (default) or "bf16" -- InferencePlan(sparse_precision=...)
         sparse_precision = kw.pop('sparse_precision', None) or ((self.test_cfg or {}).get('sparse_precision') or 'fp32')
+        # test_cfg['tta'] (optional, top level): a test-time augmentation spec, a list of (flip, angle, scale) views whose first
+        # is the identity -- InferencePlan(tta=...), for plans fed with points.  An explicit tta= (None included) overrides it
+        tta = kw.pop('tta') if 'tta' in kw else (self.test_cfg or {}).get('tta')
+        if tta is not None:
+            from .tta import check_views
+            tta = check_views(tta)
+            kw['tta'] = tta
         key = (batch_size, str(device), K.weights_generation(),
-               sum(t._version for t in list(self.parameters()) + list(self.buffers())), precision, sparse_precision)
+               sum(t._version for t in list(self.parameters()) + list(self.buffers())), precision, sparse_precision, tta)
         an_t = anchors if torch.is_tensor(anchors) else torch.as_tensor(np.asarray(anchors))
         same = self._plan is not None and self._plan_key == key and self._plan.anchors.shape == an_t.reshape(-1, 7).shape
         fp = None
@@ -977,7 +984,8 @@ class SingleStageDetector(nn.Module):
         dev = ret['voxels'].device
         anchors = ret['anchors']
         src = kwargs.get('anchors')
-        plan = self.plan(batch_size, anchors[0], dev,
+        # (voxel inputs cannot be transformed: test_cfg['tta'] applies to the plans and streams that are fed with points)
+        plan = self.plan(batch_size, anchors[0], dev, tta=None,
                          anchors_src=src[0] if isinstance(src, (list, tuple)) and len(src) else None)
         vx = self.backbone(ret['voxels'], ret['num_points'])
         plan.run_from_voxels(vx, ret['coordinates'], ret['anchors_mask'])
@@ -1004,10 +1012,14 @@ class SingleStageDetector(nn.Module):
         (score_thr, nms.iou_thr; precision / sparse_precision unless given); the voxelizer's settings and anything else
         InferencePlan accepts go through **kw.  The stream holds a copy of the weights as they are now.  `raw_cap`: the stream
         takes raw sweeps of up to that many points and crops each to its camera frustum inside the frame
-        (FrameStream(raw_cap=...): submit(clouds, frustums))."""
+        (FrameStream(raw_cap=...): submit(clouds, frustums)).  Test-time augmentation: tta= if given, else the optional
+        top-level test_cfg['tta'] (FrameStream(tta=...))."""
         from .stream import FrameStream
         precision = kw.pop('precision', None) or ((self.test_cfg or {}).get('precision') or 'fp32')
         sparse_precision = kw.pop('sparse_precision', None) or ((self.test_cfg or {}).get('sparse_precision') or 'fp32')
+        tta = kw.pop('tta') if 'tta' in kw else (self.test_cfg or {}).get('tta')
+        if tta is not None:
+            kw['tta'] = tta
         tc = self.test_cfg.get('extra', self.test_cfg) if self.test_cfg else {}
         kw.setdefault('score_thr', tc.get('score_thr', 0.3))
         kw.setdefault('iou_thr', tc.get('nms', {}).get('iou_thr', 0.1))

@@ -1,6 +1,8 @@
 """Thin torch-tensor front-end over the C ABI (include/sassd.h).  torch is used only for device memory and
 the current HIP stream; every function here launches hand-written HIP kernels from libsassd.so and raises if
 the library is missing or a call fails (no CPU fallback, no eager-PyTorch fallback)."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -175,6 +177,77 @@ def merge_sweeps(ring, slot, count, xform, T, dt, time_feature, out, n_out, stat
                                          _C.ptr(out), int(out.shape[0]), _C.ptr(n_out), _C.ptr(status), _C.stream())
     _C.check(rc, "sassd_merge_sweeps_dev")
     return out, n_out
+
+
+def _tta_host_params(views):
+    from .tta import view_params            # the spec and its rounding are stated once, there
+    p = view_params(views)
+    return p, [p[k].ctypes.data for k in ("flip", "sin", "cos", "scale")]
+
+
+def tta_views(src, n_src, views, dst, n_dst):
+    """The clouds of views 1 .. V-1 of a test-time augmentation spec (include/sassd.h "Test-time augmentation") from the
+    identity view's: `src` [cap, ndim] f32 and its device count `n_src` (one int32 word) are read; `dst` is a list of V - 1
+    clouds [>= cap, ndim] f32 and `n_dst` a list of V - 1 int32 words, which receive min(n_src, cap) rows -- x, y, z through
+    global_point, the other columns copied -- and that count.  One kernel launch whose shape depends on (cap, ndim, V)
+    only (graph-capturable), none for V == 1; no workspace."""
+    p, host = _tta_host_params(views)
+    V = len(p["flip"])
+    dst, n_dst = list(dst), list(n_dst)
+    _chk_cuda(src, n_src, *dst, *n_dst)
+    if len(dst) != V - 1 or len(n_dst) != V - 1:
+        raise ValueError("tta_views: %d views need %d destination clouds and counts, got %d and %d"
+                         % (V, V - 1, len(dst), len(n_dst)))
+    if src.dim() != 2 or src.shape[1] < 3 or src.shape[0] < 1 or src.dtype != torch.float32:
+        raise ValueError("tta_views: src must be [cap >= 1, ndim >= 3] float32, got %s %s" % (tuple(src.shape), src.dtype))
+    for d in dst:
+        if d.dim() != 2 or d.shape[1] != src.shape[1] or d.dtype != torch.float32:
+            raise ValueError("tta_views: a destination must be [rows, %d] float32, got %s %s"
+                             % (src.shape[1], tuple(d.shape), d.dtype))
+    for t in [n_src] + n_dst:
+        if t.dtype != torch.int32 or t.numel() != 1:
+            raise ValueError("tta_views: a count must be one int32 word")
+    rows = min([int(d.shape[0]) for d in dst] or [int(src.shape[0])])        # cap_dst: the shortest destination
+    dptr = (ctypes.c_void_p * max(V - 1, 1))(*[d.data_ptr() for d in dst])
+    nptr = (ctypes.c_void_p * max(V - 1, 1))(*[t.data_ptr() for t in n_dst])
+    rc = _C.lib().sassd_tta_views_dev(_C.ptr(src), int(src.shape[0]), _C.ptr(n_src), int(src.shape[1]), V, *host,
+                                      ctypes.addressof(dptr), ctypes.addressof(nptr), rows, _C.stream())
+    _C.check(rc, "sassd_tta_views_dev")
+    return dst, n_dst
+
+
+def tta_pool(guided, logits, labels, counts, views, cap_p, out=None, status=None):
+    """The candidates of the V views of every sample as one list in the sensor frame (include/sassd.h "Test-time
+    augmentation"): guided [b * V, capK, 7] f32, logits [b * V, capK] f32, labels [b * V, capK] i32, counts [b * V] i32 of the
+    inner batch -> dict(guided [b, cap_p, 7], logits [b, cap_p], labels [b, cap_p], counts [b]) (`out`: the buffers to write),
+    view-major, the boxes of views >= 1 through unview_box.  A sample with more than cap_p candidates keeps the first cap_p
+    and sets SASSD_ST_BOX_OVERFLOW in `status`.  One kernel launch (graph-capturable), no workspace."""
+    p, host = _tta_host_params(views)
+    V = len(p["flip"])
+    if guided.dim() != 3 or guided.shape[2] != 7 or guided.shape[0] % V or guided.shape[0] < V:
+        raise ValueError("tta_pool: guided must be [b * %d, capK, 7], got %s" % (V, tuple(guided.shape)))
+    bv, cap_k = int(guided.shape[0]), int(guided.shape[1])
+    b, cap_p, dev = bv // V, int(cap_p), guided.device
+    for name, t, dtype, shape in (("guided", guided, torch.float32, (bv, cap_k, 7)), ("logits", logits, torch.float32, (bv, cap_k)),
+                                  ("labels", labels, torch.int32, (bv, cap_k)), ("counts", counts, torch.int32, (bv,))):
+        if t.dtype != dtype or tuple(t.shape) != shape:
+            raise ValueError("tta_pool: %s must be %s %s, got %s %s" % (name, list(shape), dtype, tuple(t.shape), t.dtype))
+    out = dict(out or {})
+    for name, dtype, shape in (("guided", torch.float32, (b, cap_p, 7)), ("logits", torch.float32, (b, cap_p)),
+                               ("labels", torch.int32, (b, cap_p)), ("counts", torch.int32, (b,))):
+        if out.get(name) is None:
+            out[name] = torch.zeros(*shape, dtype=dtype, device=dev)
+        elif out[name].dtype != dtype or tuple(out[name].shape) != shape:
+            raise ValueError("tta_pool: out[%r] must be %s %s, got %s %s"
+                             % (name, list(shape), dtype, tuple(out[name].shape), out[name].dtype))
+    if status is None:
+        status = new_status(dev)
+    _chk_cuda(guided, logits, labels, counts, out["guided"], out["logits"], out["labels"], out["counts"], status)
+    rc = _C.lib().sassd_tta_pool(_C.ptr(guided), _C.ptr(logits), _C.ptr(labels), _C.ptr(counts), b, V, cap_k, *host,
+                                 p["angle"].ctypes.data, _C.ptr(out["guided"]), _C.ptr(out["logits"]), _C.ptr(out["labels"]),
+                                 _C.ptr(out["counts"]), cap_p, _C.ptr(status), _C.stream())
+    _C.check(rc, "sassd_tta_pool")
+    return out
 
 
 def voxel_mean(voxels, num_points, nfeat=4):

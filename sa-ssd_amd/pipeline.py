@@ -42,6 +42,7 @@ import torch
 from . import kernels as K
 from . import anchors as A
 from .stream import CALIB_DOUBLES, stage_layout
+from .tta import MAX_POOL, check_views
 
 BN_EPS = 1e-3
 
@@ -104,7 +105,7 @@ class InferencePlan:
                  iou_thr=0.1, cap_k=4096, cap_d=512, device=None, level_cap_factor=2, overlap=True, winograd=True,
                  fused_rulebooks=True, chain_bev=True, pyramid_persistent=False, spconv_cfg=None, wino4_cfg=None,
                  skip_inactive_tiles=True, rb_sync_levels=(0, 1, 2, 3), ps_tail=False, precision="fp32",
-                 sparse_precision="fp32", dense_entry=False, ps_sampled=True):
+                 sparse_precision="fp32", dense_entry=False, ps_sampled=True, tta=None):
         """precision: "fp32" (default) or "bf16" (module docstring).  In bf16 mode the fp32 kernel-selection knobs
         (winograd, chain_bev, wino4_cfg, ps_tail, skip_inactive_tiles) are ignored, and a shape the bf16 kernels do not
         support raises ValueError here (there is no fp32 fall-back).
@@ -118,15 +119,35 @@ class InferencePlan:
         part-sensitive convs there (sassd_ps_head_sampled), bit-identical to the dense kernels at every pixel that is read, so
         logits and detections are unchanged.  `ps_t` then materialises the dense maps on read.  False: the two dense launches
         in bev_and_heads (A/B, tests).  Ignored (dense) with precision="bf16", with ps_tail=True and for head shapes the
-        sampled kernel does not take."""
+        sampled kernel does not take.
+        tta: None (default) or a test-time augmentation spec, a list of 1..8 views (flip, angle, scale) whose first is the
+        identity (sassd.tta; include/sassd.h "Test-time augmentation").  The plan then takes `batch_size` clouds per frame and
+        returns `batch_size` result sets as before -- `b_user`, the outer batch: det, results(), the frame record, the
+        annotations and the staging block are sized for it -- while everything from the voxelizer to PSWarp runs on the INNER
+        batch `B` = b_user * V, inner sample s * V + v being view v of cloud s.  sassd_tta_views_dev writes the clouds of the
+        views in front of the voxelizer, sassd_tta_pool gathers the candidates of a cloud's views, back in the sensor frame,
+        into `pool` ([b_user, capP = min(V * capK, 4096)] rows) behind PSWarp, and the unchanged rescore / NMS runs on the
+        pool: the views are suppressed together.  A cloud whose views yield more than capP candidates sets
+        SASSD_ST_BOX_OVERFLOW.  The views are fixed here, for the life of the plan.  ValueError for a malformed spec and for
+        an inner batch the sparse index space cannot hold, before anything is allocated."""
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32' or 'bf16', got %r" % (precision,))
         if sparse_precision not in ("fp32", "bf16"):
             raise ValueError("sparse_precision must be 'fp32' or 'bf16', got %r" % (sparse_precision,))
         self.precision, self.bf16 = precision, precision == "bf16"
         self.sparse_precision, self.sparse_bf16 = sparse_precision, sparse_precision == "bf16"
+        # b_user: the clouds per frame and the result sets per frame (the outer batch).  B: the samples the detector runs
+        # on (the inner batch), b_user * V under test-time augmentation and b_user otherwise
+        self.tta = None if tta is None else check_views(tta)
+        self.V = 1 if self.tta is None else len(self.tta)
+        self.b_user = int(batch_size)
+        if self.tta is not None:
+            cells = float(np.prod([float(v) for v in sparse_shape])) * self.b_user * self.V
+            if self.b_user < 1 or cells >= 4294967294.0:        # lin_fits of csrc/rulebook.hip: linear voxel indices are 32-bit
+                raise ValueError("tta: %d views of %d clouds are an inner batch of %d samples, which a sparse shape of %s "
+                                 "cannot index" % (self.V, self.b_user, self.b_user * self.V, tuple(sparse_shape)))
         dev = torch.device(device if device is not None else "cuda:0")
-        self.dev, self.B, self.ncls, self.A = dev, int(batch_size), int(num_class), int(anchors_per_loc)
+        self.dev, self.B, self.ncls, self.A = dev, self.b_user * self.V, int(num_class), int(anchors_per_loc)
         self.voxel_size = np.asarray(voxel_size, np.float32)
         self.pc_range = np.asarray(point_cloud_range, np.float32)
         self.T, self.max_voxels = int(max_num_points), int(max_voxels)
@@ -231,8 +252,14 @@ class InferencePlan:
         self.df = dict(guided=z(B, self.capK, 7), labels=z(B, self.capK, dt=i32), scores=z(B, self.capK),
                        counts=z(B, dt=i32))
         self.logits = z(B, self.capK)
-        self.det = dict(boxes=z(B, self.capD, 7), scores=z(B, self.capD), labels=z(B, self.capD, dt=i32),
-                        counts=z(B, dt=i32))
+        # test-time augmentation: the candidates of a cloud's views, pooled for one rescore / NMS per cloud
+        self.capP, self.pool, bu = None, None, self.b_user
+        if self.tta is not None:
+            self.capP = min(self.V * self.capK, MAX_POOL)
+            self.pool = dict(guided=z(bu, self.capP, 7), logits=z(bu, self.capP), labels=z(bu, self.capP, dt=i32),
+                             counts=z(bu, dt=i32))
+        self.det = dict(boxes=z(bu, self.capD, 7), scores=z(bu, self.capD), labels=z(bu, self.capD, dt=i32),
+                        counts=z(bu, dt=i32))
         self.middle = {}
         # all seven rulebooks through the fused pyramid (1 fill + 8 launches); the per-op chain (30) stays selectable for A/B
         self.pyr = None
@@ -407,7 +434,8 @@ class InferencePlan:
     # ------------------------------------------------------------------------------------------------
     def voxelize(self, clouds, n_dev=None):
         """clouds: list of B device tensors [Ni, ndim] f32.  Fills idx[0] (b,z,y,x), mean, row_off.  With `n_dev`
-        (device int32 [B]) the clouds are capacity-sized staging buffers holding n_dev[b] points each."""
+        (device int32 [B], or a list of B one-word tensors) the clouds are capacity-sized staging buffers holding n_dev[b]
+        points each."""
         assert len(clouds) == self.B
         for pts in clouds:
             if pts.shape[1] < self.cin:
@@ -420,7 +448,7 @@ class InferencePlan:
                        out=dict(coors=self.idx[0], mean=self.mean, voxel_num=self.vnum[b:b + 1],
                                 num_points=self._numpts()),
                        row_offset=self.row_off[b:b + 2], status=self.status, cap=self.caps[0],
-                       n_dev=None if n_dev is None else n_dev[b:b + 1])
+                       n_dev=None if n_dev is None else n_dev[b] if isinstance(n_dev, (list, tuple)) else n_dev[b:b + 1])
         self._seg("voxelize", e0)
 
     def _numpts(self):
@@ -430,6 +458,8 @@ class InferencePlan:
 
     def load_voxels(self, voxel_feats, coors4):
         """Reference-style inputs (single_stage.py:110-117): mean features [M,Cin] and coords [M,4] (b,z,y,x)."""
+        if self.tta is not None:
+            raise RuntimeError("a plan with tta transforms point clouds: it has no voxel entry (run_from_points, capture)")
         m = voxel_feats.shape[0]
         if voxel_feats.dim() != 2 or voxel_feats.shape[1] != self.cin:
             raise ValueError("the plan reads %d features per voxel, got features of shape %s"
@@ -665,7 +695,12 @@ class InferencePlan:
                               self.ps_list, self._ps_t[1])
         K.pswarp_sample(self._ps_t[1], self.df["guided"], self.df["counts"], self.capK, self.grid_offsets,
                         self.spatial_scale, self.logits)
-        K.rescore_nms(self.df["guided"], self.logits, self.df["labels"], self.df["counts"], self.score_thr,
+        cand, logits = self.df, self.logits
+        if self.tta is not None:        # the views of a cloud as one candidate list in the sensor frame: pooled NMS
+            cand = K.tta_pool(self.df["guided"], self.logits, self.df["labels"], self.df["counts"], self.tta, self.capP,
+                              out=self.pool, status=self.status)
+            logits = cand["logits"]
+        K.rescore_nms(cand["guided"], logits, cand["labels"], cand["counts"], self.score_thr,
                       self.iou_thr, self.capD, self.det, self.status)
         self._seg("post", e0)
 
@@ -706,10 +741,25 @@ class InferencePlan:
         self.post()
         return self.det
 
+    def _view_clouds(self, clouds):
+        """The inner batch of an eager frame: every cloud followed by its views 1 .. V-1 (sassd_tta_views_dev)."""
+        if self.tta is None:
+            return clouds
+        if len(clouds) != self.b_user:
+            raise ValueError("a batch of %d clouds for a plan of batch_size %d" % (len(clouds), self.b_user))
+        inner = []
+        for pts in clouds:
+            views = [torch.empty_like(pts) for _ in range(self.V - 1)]
+            if self.V > 1 and pts.shape[0]:
+                n = torch.full((self.V,), int(pts.shape[0]), dtype=torch.int32, device=self.dev)
+                K.tta_views(pts, n[0:1], self.tta, views, [n[v:v + 1] for v in range(1, self.V)])
+            inner += [pts] + views
+        return inner
+
     def run_from_points(self, clouds, anchors_mask=None):
         """One frame batch, raw device point clouds in -> device detection buffers out (no host sync)."""
         with K.ws_scope(self._wsid):
-            self.voxelize(clouds)
+            self.voxelize(self._view_clouds(clouds))
             self.backbone(anchors_mask=anchors_mask)
             return self._tail(anchors_mask)
 
@@ -746,7 +796,11 @@ class InferencePlan:
         `sw_count`, `sw_xform` [B,S] i32, `sw_T` [B,S,3,4] f64, `sw_dt` [B,S] f32 -- are views into the staging block; the
         frame's first nodes are one sassd_merge_sweeps_dev per sample (one kernel each), which write `pts_in[b]` and `npts[b]`
         for the unchanged voxelizer.  A merged cloud above points_cap sets SASSD_ST_POINT_OVERFLOW.  `npts` is a tensor of its
-        own; the block's counts are not read by the frame.  Excludes raw_cap."""
+        own; the block's counts are not read by the frame.  Excludes raw_cap.
+        A plan with tta (class docstring) is fed exactly like one without: `pts_in`, `npts`, `raw_in`, the ring, the staging
+        block and the record are those of its b_user clouds.  Behind the crop / merge nodes and in front of the voxelizer the
+        frame holds one sassd_tta_views_dev per cloud, which writes `pts_views[b][v - 1]` and `npts_views[b, v - 1]` from
+        `pts_in[b]` and `npts[b]`; the voxelizer reads all B clouds."""
         dev = self.dev
         S, self.sw_ring = 0, None
         if sweeps is not None:
@@ -755,7 +809,7 @@ class InferencePlan:
             ring, S, tf = sweeps["ring"], int(sweeps["S"]), bool(sweeps["time_feature"])
             if "voxelize" not in stages or not 1 <= S <= 16:
                 raise ValueError("sweeps needs 1..16 entries and the voxelize stage")
-            if (ring.dim() != 4 or ring.shape[0] != self.B or ring.shape[2] != int(sweeps["sweep_cap"])
+            if (ring.dim() != 4 or ring.shape[0] != self.b_user or ring.shape[2] != int(sweeps["sweep_cap"])
                     or ring.dtype != torch.float32 or not ring.is_cuda or not ring.is_contiguous()):
                 raise ValueError("sweeps: the ring must be a contiguous [B, R, sweep_cap, ndim_in] float32 device tensor")
             ndim_out = ring.shape[3] + (1 if tf else 0)
@@ -769,49 +823,60 @@ class InferencePlan:
         self.raw_cap = None if raw_cap is None else int(raw_cap)
         if self.raw_cap is not None and (self.raw_cap < 1 or "voxelize" not in stages):
             raise ValueError("raw_cap must be >= 1 and needs the voxelize stage")
-        self.pts_in = [torch.zeros(self.pts_cap, ndim, dtype=torch.float32, device=dev) for _ in range(self.B)]
-        L = stage_layout(self.B, self.raw_cap is not None, annos, seal, **(dict(sweeps=S) if S else {}))
+        bu, V = self.b_user, self.V
+        self.pts_in = [torch.zeros(self.pts_cap, ndim, dtype=torch.float32, device=dev) for _ in range(bu)]
+        L = stage_layout(bu, self.raw_cap is not None, annos, seal, **(dict(sweeps=S) if S else {}))
         block = self._stage_block = torch.zeros(L["total"], dtype=torch.uint8, device=dev)
-        counts = block[L["counts"]:L["counts"] + 4 * self.B].view(torch.int32)
+        counts = block[L["counts"]:L["counts"] + 4 * bu].view(torch.int32)
         if seal:
             self._seq = block[L["seq"]:L["counts"]].view(torch.int32)
         if annos:
-            self.calib = block[L["calib"]:L.get("sweep_T", L["words"])].view(torch.float64).view(self.B, CALIB_DOUBLES)
+            self.calib = block[L["calib"]:L.get("sweep_T", L["words"])].view(torch.float64).view(bu, CALIB_DOUBLES)
         if self.raw_cap is not None:
-            self.raw_in = [torch.zeros(self.raw_cap, ndim, dtype=torch.float32, device=dev) for _ in range(self.B)]
-            self.crop_planes = block[L["planes"]:L["calib"]].view(torch.float64).view(self.B, 6, 4)
+            self.raw_in = [torch.zeros(self.raw_cap, ndim, dtype=torch.float32, device=dev) for _ in range(bu)]
+            self.crop_planes = block[L["planes"]:L["calib"]].view(torch.float64).view(bu, 6, 4)
             self.crop_f32_math = False
             self.nraw = counts
-            self.npts = torch.zeros(self.B, dtype=torch.int32, device=dev)      # written by the crop, read by the voxelizer
+            self.npts = torch.zeros(bu, dtype=torch.int32, device=dev)      # written by the crop, read by the voxelizer
         elif S:
             self.sw_ring, self.sw_time = ring, tf
-            self.sw_T = block[L["sweep_T"]:L["words"]].view(torch.float64).view(self.B, S, 3, 4)
+            self.sw_T = block[L["sweep_T"]:L["words"]].view(torch.float64).view(bu, S, 3, 4)
             self.sw_slot, self.sw_count, self.sw_xform = (
-                block[L[k]:L[k] + 4 * self.B * S].view(torch.int32).view(self.B, S)
+                block[L[k]:L[k] + 4 * bu * S].view(torch.int32).view(bu, S)
                 for k in ("sweep_slot", "sweep_count", "sweep_xform"))
-            self.sw_dt = block[L["sweep_dt"]:L["total"]].view(torch.float32).view(self.B, S)
+            self.sw_dt = block[L["sweep_dt"]:L["total"]].view(torch.float32).view(bu, S)
             self.sw_slot.fill_(-1)                  # until the first descriptors arrive, every entry is absent
-            self.npts = torch.zeros(self.B, dtype=torch.int32, device=dev)      # written by the merge, read by the voxelizer
+            self.npts = torch.zeros(bu, dtype=torch.int32, device=dev)      # written by the merge, read by the voxelizer
         else:
             self.npts = counts
         if annos:
-            self.record = torch.zeros(K.frame_record_kitti_bytes(self.B, self.capD), dtype=torch.uint8, device=dev)
+            self.record = torch.zeros(K.frame_record_kitti_bytes(bu, self.capD), dtype=torch.uint8, device=dev)
         elif seal:
-            self.record = torch.zeros(K.frame_record_bytes(self.B, self.capD), dtype=torch.uint8, device=dev)
+            self.record = torch.zeros(K.frame_record_bytes(bu, self.capD), dtype=torch.uint8, device=dev)
+        # test-time augmentation: `pts_in` / `npts` stay the clouds the caller (or the crop, or the merge) fills -- the identity
+        # views; the other views have staging of their own, written inside the frame, and the voxelizer reads all B of them
+        self.pts_views = [[torch.zeros(self.pts_cap, ndim, dtype=torch.float32, device=dev) for _ in range(V - 1)]
+                          for _ in range(bu)]
+        self.npts_views = torch.zeros(bu, V - 1, dtype=torch.int32, device=dev) if V > 1 else None
+        pts_inner = [t for b in range(bu) for t in [self.pts_in[b]] + self.pts_views[b]]
+        npts_inner = [t for b in range(bu) for t in [self.npts[b:b + 1]] + [self.npts_views[b, v:v + 1] for v in range(V - 1)]]
         assert self.prof is None, "per-stage event timing and graph capture exclude each other"
 
         def frame():
             with K.ws_scope(self._wsid):
                 if self.raw_cap is not None:
-                    for b in range(self.B):
+                    for b in range(bu):
                         K.crop_polytope(self.raw_in[b], self.nraw[b:b + 1], self.crop_planes[b], self.crop_f32_math,
                                         self.pts_in[b], self.npts[b:b + 1], self.status)
                 if S:
-                    for b in range(self.B):
+                    for b in range(bu):
                         K.merge_sweeps(self.sw_ring[b], self.sw_slot[b], self.sw_count[b], self.sw_xform[b], self.sw_T[b],
                                        self.sw_dt[b], self.sw_time, self.pts_in[b], self.npts[b:b + 1], self.status)
+                if V > 1 and "voxelize" in stages:
+                    for b in range(bu):
+                        K.tta_views(self.pts_in[b], self.npts[b:b + 1], self.tta, self.pts_views[b], npts_inner[b * V + 1:(b + 1) * V])
                 if "voxelize" in stages:
-                    self.voxelize(self.pts_in, n_dev=self.npts)
+                    self.voxelize(pts_inner, n_dev=self.npts if self.tta is None else npts_inner)
                 if "backbone" in stages:
                     self.backbone()
                 elif "sparse" in stages:              # rulebooks + the 14 sparse convs only (roofline measurement)
@@ -871,7 +936,7 @@ class InferencePlan:
         if st:
             raise RuntimeError("sassd pipeline status flags 0x%x (capacity overflow / hash full)" % st)
         out = []
-        for b in range(self.B):
+        for b in range(self.b_user):
             k = int(counts[b])
             if k == 0:
                 out.append((None, None, None))

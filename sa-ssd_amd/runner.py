@@ -59,7 +59,7 @@ def train_model(model, optimizer, train_loader, lr_scheduler, sync, start_epoch,
 
 
 def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=None, world=None, inflight=0,
-                points_cap=None, raw_prefix=None, device_annos=False, ndim=4):
+                points_cap=None, raw_prefix=None, device_annos=False, ndim=4, tta=None):
     """Run the detector over `dataset` (test mode) -> list of KITTI result annotations in dataset order on every rank
     (this rank's frames are computed here, the others' gathered from their ranks).  `saveto`: also write result files.
     inflight > 0: the frames' raw points go through model.frame_stream(...) with that many frames in flight (1..4) instead of
@@ -75,7 +75,10 @@ def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=N
     img_shape, so the camera-frame annotation (location, alpha, the clipped 2-D box, the keep test) is computed inside the
     captured frame and only assembled on the host (kitti_common.result_anno_from_cam); False keeps kitti_bbox2results.
     `ndim` (with inflight > 0): float32 columns per point of the clouds the dataset loads (4: KITTI; a detector built with
-    num_input_features = 5..8 needs at least that many)."""
+    num_input_features = 5..8 needs at least that many).
+    `tta` (with inflight > 0): a test-time augmentation spec (sassd.tta: a list of (flip, angle, scale) views, the first the
+    identity) -- the stream detects on every view inside the captured frame and suppresses the views' candidates together.
+    None leaves it to the model's test_cfg['tta']."""
     if rank is None or world is None:
         rank, _, world = D.env_world() if D.dist.is_initialized() else (0, 0, 1)
     if class_names is not None:
@@ -85,7 +88,9 @@ def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=N
     annos = []
     with torch.no_grad():
         if inflight:
-            annos = _stream_test(model, dataset, mine, workers, inflight, points_cap, raw_prefix, device_annos, ndim)
+            annos = _stream_test(model, dataset, mine, workers, inflight, points_cap, raw_prefix, device_annos, ndim, tta)
+        elif tta is not None:
+            raise ValueError("tta needs inflight > 0 (the views are made inside the captured frame of a FrameStream)")
         elif device_annos:
             raise ValueError("device_annos needs inflight > 0 (the annotations are written by the captured frame of a FrameStream)")
         elif raw_prefix is not None:
@@ -102,7 +107,8 @@ def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=N
     return merged
 
 
-def _stream_test(model, dataset, indices, workers, inflight, points_cap=None, raw_prefix=None, device_annos=False, ndim=4):
+def _stream_test(model, dataset, indices, workers, inflight, points_cap=None, raw_prefix=None, device_annos=False, ndim=4,
+                 tta=None):
     """single_test's frames through a FrameStream: the point files are read ahead on `workers` threads, submitted as host
     clouds, and every result becomes the annotation forward_test builds for the frame's img_meta.  `ndim`: float32 columns
     per point of the files and of the clouds load_frame returns (4: KITTI)."""
@@ -131,6 +137,7 @@ def _stream_test(model, dataset, indices, workers, inflight, points_cap=None, ra
                             **({} if ndim == 4 else dict(ndim=ndim)),
                             **({} if raw_cap is None else dict(raw_cap=raw_cap)),
                             **(dict(annos=True) if device_annos else {}),
+                            **({} if tta is None else dict(tta=tta)),
                             anchors_bv=dataset.anchors_bv, voxel_size=tuple(gen.voxel_size),
                             point_cloud_range=tuple(gen.point_cloud_range), max_num_points=gen.max_num_points_per_voxel,
                             max_voxels=gen._max_voxels, anchor_area_threshold=dataset.anchor_area_threshold)

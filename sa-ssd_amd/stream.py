@@ -538,7 +538,7 @@ class _PlanSlot:
     def __init__(self, plan, points_cap, ndim, raw_cap=None, annos=False, sweeps=None):
         import torch
         self.torch, self.plan = torch, plan
-        dev, B = plan.dev, plan.B
+        dev, B = plan.dev, plan.b_user               # the clouds of a frame (a plan with tta runs more samples inside)
         self.stream = torch.cuda.Stream(device=dev)
         self.sw = sweeps
         kw = dict(annos=True) if annos else {}
@@ -571,7 +571,7 @@ class _PlanSlot:
         if self.sw is None:
             if sweeps is not None:
                 raise ValueError("sweeps given to a stream built without sweeps= (its clouds are taken as they are)")
-            checked = check_frame_inputs(clouds, frustums, plan.B, self.ndim, self.cap, self.raw_cap, calibs,
+            checked = check_frame_inputs(clouds, frustums, plan.b_user, self.ndim, self.cap, self.raw_cap, calibs,
                                          self.annos)                                         # nothing is queued before this
             planes, calib = checked if self.annos else (checked, None)
             dev_pts = self.dev_pts
@@ -580,12 +580,12 @@ class _PlanSlot:
                 raise ValueError("frustums given to a stream with sweeps (merged clouds are not cropped)")
             book = self.sw["book"]
             d = book.plan(clouds, sweeps)                                                    # nothing is queued before this,
-            planes, calib = None, _check_calibs(calibs, None, plan.B, self.annos)            # and the book is unchanged
+            planes, calib = None, _check_calibs(calibs, None, plan.b_user, self.annos)            # and the book is unchanged
             assert (d["k"] + 1) & _SEQ_MASK == seq      # ticket t carries sweep t - 1: frame t - inflight, the last reader of
             book.commit(d)                              # the ring slot written now, ran on this slot's stream
             for key in ("slot", "count", "xform", "T", "dt"):
                 view["sweep_" + key][...] = d[key]
-            dev_pts = [self.sw["ring"][b, d["write"]] for b in range(plan.B)]
+            dev_pts = [self.sw["ring"][b, d["write"]] for b in range(plan.b_user)]
         if planes is not None:
             view["planes"][...] = planes
         if calib is not None:
@@ -693,12 +693,22 @@ class FrameStream:
     of sweep k - R; the last frame that read that one is the frame of sweep k - R + S - 1 = k - inflight, ticket
     t - inflight, which ran on this same slot and stream, so stream order covers it; the frames that may still run on the
     other streams, tickets t - inflight + 1 .. t - 1, read no sweep older than k - R + 1.  This holds because every ticket
-    writes exactly one sweep (a refused submit uses neither) -- the slot asserts it."""
+    writes exactly one sweep (a refused submit uses neither) -- the slot asserts it.
+
+    Test-time augmentation: FrameStream(..., tta=[(0, 0.0, 1.0), (1, 0.0, 1.0), ...]) -- 1..8 views (flip, angle, scale), the
+    first the identity (sassd.tta) -- detects on every view of every cloud inside the captured frame and suppresses the
+    candidates of a cloud's views together (InferencePlan(tta=...); include/sassd.h "Test-time augmentation").  submit and
+    collect are unchanged: batch_size clouds in, batch_size result sets out; the views are fixed for the life of the
+    stream.  Composes with raw_cap, annos, sweeps, precision and sparse_precision: the views are made from the cropped /
+    merged cloud.  A malformed spec raises ValueError here, before anything is allocated."""
 
     def __init__(self, state_dict, inflight=3, points_cap=None, batch_size=1, anchors=None, device=None, ndim=4,
-                 raw_cap=None, annos=False, sweeps=None, sweep_cap=None, time_feature=True, **plan_kwargs):
+                 raw_cap=None, annos=False, sweeps=None, sweep_cap=None, time_feature=True, tta=None, **plan_kwargs):
         from .pipeline import InferencePlan, input_features_of
         cin = input_features_of(state_dict)
+        if tta is not None:
+            from .tta import check_views
+            tta = check_views(tta)
         if sweeps is not None:
             if not 1 <= int(sweeps) <= MAX_SWEEPS:
                 raise ValueError("sweeps must be 1..%d, got %d" % (MAX_SWEEPS, int(sweeps)))
@@ -724,8 +734,9 @@ class FrameStream:
         self.raw_cap = None if raw_cap is None else int(raw_cap)
         self.annos = bool(annos)
         self.plans = [InferencePlan(state_dict, batch_size=batch_size, anchors=anchors, device=device,
-                                    overlap=inflight == 1, **plan_kwargs) for _ in range(inflight)]
-        B, capD = self.plans[0].B, self.plans[0].capD
+                                    overlap=inflight == 1, **({} if tta is None else dict(tta=tta)), **plan_kwargs)
+                      for _ in range(inflight)]
+        B, capD = self.plans[0].b_user, self.plans[0].capD
         self.sweeps = None if sweeps is None else int(sweeps)
         extra = {}
         if self.sweeps is not None:
