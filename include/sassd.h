@@ -765,6 +765,45 @@ int sassd_rescore_nms(const float *guided, const float *logits, const int32_t *l
                       int capD, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Box fusion (opt-in): behind sassd_rescore_nms every detection becomes the score-weighted mean of the candidates it
+ * stands for -- its own box and the overlapping boxes of its label that NMS dropped -- instead of the single survivor.
+ * Under test-time augmentation the candidate list is the pool of all views, so the views' boxes are averaged.  Scores,
+ * labels, counts and the order of the detections are not touched; only boxes move.  (The reference keeps the survivor.)
+ *
+ * CONTRACT  (the rule is csrc/box_fuse_core.h; its numpy statement is sassd.fuse.fuse_host)
+ *   inputs     the candidate buffers exactly as handed to sassd_rescore_nms: guided [B,capK,7] f32, logits [B,capK] f32,
+ *              labels [B,capK] i32, counts [B] i32, score_thr; and the buffers it left behind: det_boxes [B,capD,7] f32,
+ *              det_labels [B,capD] i32, det_counts [B] i32.  Detection d of sample b is row t < clamp(det_counts[b], 0,
+ *              capD) with box B_d and label l_d; candidate j is row j < clamp(counts[b], 0, capK) with score
+ *              s_j = sigmoidf(logits[j]) (csrc/sigmoid.h, the fp32 function sassd_rescore_nms thresholds and sorts by).
+ *   member     candidate j is a member of d when s_j > score_thr, labels[j] == l_d and
+ *              iou3d::iou_bev(bev(B_d), bev(box_j)) >= fuse_iou -- the detection first, the candidate second, bev(g) =
+ *              (x - w/2, y - l/2, x + w/2, y + l/2, yaw) as sassd_rescore_nms builds it.  A NaN IoU is not a member.
+ *   sums       float64, over the members in ASCENDING j, every product, quotient and sum rounded on its own (no fused
+ *              multiply-add); the sum of one term is that term.  W = sum s_j;  F_q = sum s_j * f_jq for q in x, y, z, w, l,
+ *              h (each product is exact);  delta_j = d - pi * floor(d / pi + 0.5) with d = yaw_j - yaw_d and float64 pi,
+ *              so delta_j lies in [-pi/2, pi/2) and a candidate pointing the opposite way (a flipped view's) does not drag
+ *              the heading round;  D = sum s_j * delta_j.
+ *   result     fused_q = float32(F_q / W), fused_yaw = float32(double(yaw_d) + D / W).  Without a member, or when W is not a
+ *              positive finite number, fused row = B_d bit for bit.  A detection whose only member is itself comes out bit
+ *              for bit too, by arithmetic ((s * f) / s == f), except that a yaw of -0.0 becomes +0.0.
+ *   output     fused [B,capD,7] f32, a buffer of its own (det_boxes stays readable); rows at and past the detection count
+ *              are not written.
+ *   launches   one kernel, no workspace: (ceil(capD / 4), B) workgroups of 4 waves, one wave per detection; the lanes take
+ *              the candidates 64 at a time and ballot the members, whose terms are then added serially, lowest row first --
+ *              the result is a pure function of the inputs.  No host sync, no allocation, no memset, no atomics, no
+ *              workgroup waits for another.
+ *   errors     SASSD_EINVAL before any HIP call: a NULL or misaligned (4 bytes) pointer, batch / capK / capD < 1, batch >
+ *              65535, capK > 4096, fuse_iou not inside (0, 1) or not finite, fused overlapping det_boxes.
+ * sassd_candidate_scores: scores[i] = sigmoidf(logits[i]) for i < n -- the s_j above as a tensor, for callers that state
+ * the rule on the host (one kernel, one thread per element; n == 0 launches nothing).
+ * ---------------------------------------------------------------------------------------------- */
+int sassd_box_fuse(const float *guided, const float *logits, const int32_t *labels, const int32_t *counts, int batch,
+                   int capK, float score_thr, float fuse_iou, const float *det_boxes, const int32_t *det_labels,
+                   const int32_t *det_counts, int capD, float *fused, void *stream);
+int sassd_candidate_scores(const float *logits, long long n, float *scores, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Frame record: the LAST node of a captured frame.  sassd_frame_seal copies the detection buffers sassd_rescore_nms
  * left behind into ONE fixed-size, self-describing device record, so that a frame leaves the GPU in one asynchronous
  * copy (sassd.stream.FrameStream; the reference reads its detections with three blocking copies per sample,

@@ -49,6 +49,9 @@ _SIGS = {
     # test-time augmentation (include/sassd.h "Test-time augmentation")
     "sassd_tta_views_dev": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "sassd_tta_pool": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
+    # box fusion behind rescore / NMS (include/sassd.h "Box fusion")
+    "sassd_box_fuse": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _I, _P, _P]),
+    "sassd_candidate_scores": (_I, [_P, C.c_longlong, _P, _P]),
     "sassd_hash_bytes": (_SZ, [_I]),
     "sassd_hash_build": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P, _P]),
     "sassd_rulebook_subm": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P, _P]),

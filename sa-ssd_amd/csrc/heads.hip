@@ -10,12 +10,11 @@
 // rank sort; the NMS suppression word of a (row, 64-column block) is one wave64 ballot.
 #include "common.h"
 #include "iou3d_device.h"
+#include "sigmoid.h"
 
 namespace {
 
 constexpr float kPi = 3.14159265358979323846f;      // float(np.pi)
-
-__device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // ------------------------------------------------------------------------------------------------
 // decode + filter

@@ -898,8 +898,16 @@ class SingleStageDetector(nn.Module):
             from .tta import check_views
             tta = check_views(tta)
             kw['tta'] = tta
+        # test_cfg['fuse_iou'] (optional, top level): box fusion behind NMS -- InferencePlan(fuse_iou=...).  An explicit
+        # fuse_iou= (None included) overrides it
+        fuse_iou = kw.pop('fuse_iou') if 'fuse_iou' in kw else (self.test_cfg or {}).get('fuse_iou')
+        if fuse_iou is not None:
+            from .fuse import check_fuse_iou
+            fuse_iou = check_fuse_iou(fuse_iou)
+            kw['fuse_iou'] = fuse_iou
         key = (batch_size, str(device), K.weights_generation(),
-               sum(t._version for t in list(self.parameters()) + list(self.buffers())), precision, sparse_precision, tta)
+               sum(t._version for t in list(self.parameters()) + list(self.buffers())), precision, sparse_precision, tta,
+               fuse_iou)
         an_t = anchors if torch.is_tensor(anchors) else torch.as_tensor(np.asarray(anchors))
         same = self._plan is not None and self._plan_key == key and self._plan.anchors.shape == an_t.reshape(-1, 7).shape
         fp = None
@@ -1013,13 +1021,17 @@ class SingleStageDetector(nn.Module):
         InferencePlan accepts go through **kw.  The stream holds a copy of the weights as they are now.  `raw_cap`: the stream
         takes raw sweeps of up to that many points and crops each to its camera frustum inside the frame
         (FrameStream(raw_cap=...): submit(clouds, frustums)).  Test-time augmentation: tta= if given, else the optional
-        top-level test_cfg['tta'] (FrameStream(tta=...))."""
+        top-level test_cfg['tta'] (FrameStream(tta=...)).  Box fusion: fuse_iou= if given (None: off), else the optional
+        top-level test_cfg['fuse_iou'] (FrameStream(fuse_iou=...))."""
         from .stream import FrameStream
         precision = kw.pop('precision', None) or ((self.test_cfg or {}).get('precision') or 'fp32')
         sparse_precision = kw.pop('sparse_precision', None) or ((self.test_cfg or {}).get('sparse_precision') or 'fp32')
         tta = kw.pop('tta') if 'tta' in kw else (self.test_cfg or {}).get('tta')
         if tta is not None:
             kw['tta'] = tta
+        fuse_iou = kw.pop('fuse_iou') if 'fuse_iou' in kw else (self.test_cfg or {}).get('fuse_iou')
+        if fuse_iou is not None:
+            kw['fuse_iou'] = fuse_iou
         tc = self.test_cfg.get('extra', self.test_cfg) if self.test_cfg else {}
         kw.setdefault('score_thr', tc.get('score_thr', 0.3))
         kw.setdefault('iou_thr', tc.get('nms', {}).get('iou_thr', 0.1))

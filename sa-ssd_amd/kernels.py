@@ -1223,6 +1223,58 @@ def rescore_nms(guided, logits, labels, counts, score_thr, iou_thr, cap_d, out=N
     return dict(boxes=boxes, scores=scores, labels=olabels, counts=ocounts)
 
 
+def box_fuse(guided, logits, labels, counts, score_thr, fuse_iou, det, out=None):
+    """Box fusion behind rescore_nms (include/sassd.h "Box fusion"): the candidate buffers exactly as they were handed to
+    rescore_nms -- guided [b, capK <= 4096, 7] f32, logits [b, capK] f32, labels [b, capK] i32, counts [b] i32, score_thr -- and
+    the dict `det` it returned -> fused boxes [b, capD, 7] f32 (`out`: the buffer to write; not det["boxes"]).  Row t below the
+    detection count becomes the score-weighted float64 mean, in ascending candidate row, of the candidates of its label whose
+    rotated BEV IoU with it is >= fuse_iou (sassd.fuse.fuse_host states it); rows at and past the count are not written.
+    `det` is only read.  One kernel launch (graph-capturable), no workspace."""
+    from .fuse import check_fuse_iou, MAX_CANDIDATES       # the switch is stated once, there
+    fuse_iou = check_fuse_iou(fuse_iou)
+    if fuse_iou is None:
+        raise ValueError("box_fuse: fuse_iou must be a number inside (0, 1), got None")
+    if guided.dim() != 3 or guided.shape[2] != 7 or guided.shape[0] < 1 or not 1 <= guided.shape[1] <= MAX_CANDIDATES:
+        raise ValueError("box_fuse: guided must be [b >= 1, 1 <= capK <= %d, 7], got %s" % (MAX_CANDIDATES, tuple(guided.shape)))
+    b, cap_k = int(guided.shape[0]), int(guided.shape[1])
+    boxes = det["boxes"]
+    if boxes.dim() != 3 or boxes.shape[0] != b or boxes.shape[1] < 1 or boxes.shape[2] != 7:
+        raise ValueError("box_fuse: det['boxes'] must be [%d, capD >= 1, 7], got %s" % (b, tuple(boxes.shape)))
+    cap_d = int(boxes.shape[1])
+    for name, t, dtype, shape in (("guided", guided, torch.float32, (b, cap_k, 7)), ("logits", logits, torch.float32, (b, cap_k)),
+                                  ("labels", labels, torch.int32, (b, cap_k)), ("counts", counts, torch.int32, (b,)),
+                                  ("det['boxes']", boxes, torch.float32, (b, cap_d, 7)),
+                                  ("det['labels']", det["labels"], torch.int32, (b, cap_d)),
+                                  ("det['counts']", det["counts"], torch.int32, (b,))):
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError("box_fuse: %s must be a contiguous %s %s, got %s %s" % (name, list(shape), dtype, tuple(t.shape), t.dtype))
+    if out is None:
+        out = torch.zeros(b, cap_d, 7, dtype=torch.float32, device=guided.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (b, cap_d, 7) or not out.is_contiguous():
+        raise ValueError("box_fuse: out must be a contiguous %s float32, got %s %s" % ([b, cap_d, 7], tuple(out.shape), out.dtype))
+    if out.data_ptr() == boxes.data_ptr():
+        raise ValueError("box_fuse: out must not be det['boxes'] (the fusion is not done in place)")
+    _chk_cuda(guided, logits, labels, counts, boxes, det["labels"], det["counts"], out)
+    rc = _C.lib().sassd_box_fuse(_C.ptr(guided), _C.ptr(logits), _C.ptr(labels), _C.ptr(counts), b, cap_k, float(score_thr),
+                                 fuse_iou, _C.ptr(boxes), _C.ptr(det["labels"]), _C.ptr(det["counts"]), cap_d, _C.ptr(out),
+                                 _C.stream())
+    _C.check(rc, "sassd_box_fuse")
+    return out
+
+
+def candidate_scores(logits):
+    """sigmoidf of every logit (float32 tensor of any shape): the scores rescore_nms thresholds and sorts by and box_fuse
+    weights by, to the bit.  One kernel launch."""
+    _chk_cuda(logits)
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("candidate_scores: logits must be a contiguous float32 tensor, got %s" % (logits.dtype,))
+    out = torch.empty_like(logits)
+    if logits.numel():
+        rc = _C.lib().sassd_candidate_scores(_C.ptr(logits), logits.numel(), _C.ptr(out), _C.stream())
+        _C.check(rc, "sassd_candidate_scores")
+    return out
+
+
 def frame_record_bytes(batch, cap_d):
     """Size of the frame record of include/sassd.h ("Frame record") for `batch` samples of `cap_d` detection rows."""
     n = int(_C.lib().sassd_frame_record_bytes(int(batch), int(cap_d)))

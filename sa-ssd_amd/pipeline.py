@@ -42,6 +42,7 @@ import torch
 from . import kernels as K
 from . import anchors as A
 from .stream import CALIB_DOUBLES, stage_layout
+from .fuse import check_fuse_iou
 from .tta import MAX_POOL, check_views
 
 BN_EPS = 1e-3
@@ -105,7 +106,8 @@ class InferencePlan:
                  iou_thr=0.1, cap_k=4096, cap_d=512, device=None, level_cap_factor=2, overlap=True, winograd=True,
                  fused_rulebooks=True, chain_bev=True, pyramid_persistent=False, spconv_cfg=None, wino4_cfg=None,
                  skip_inactive_tiles=True, rb_sync_levels=(0, 1, 2, 3), ps_tail=False, precision="fp32",
-                 sparse_precision="fp32", dense_entry=False, ps_sampled=True, tta=None):
+                 sparse_precision="fp32", dense_entry=False, ps_sampled=True, tta=None,
+                 fuse_iou=None):
         """precision: "fp32" (default) or "bf16" (module docstring).  In bf16 mode the fp32 kernel-selection knobs
         (winograd, chain_bev, wino4_cfg, ps_tail, skip_inactive_tiles) are ignored, and a shape the bf16 kernels do not
         support raises ValueError here (there is no fp32 fall-back).
@@ -129,7 +131,14 @@ class InferencePlan:
         into `pool` ([b_user, capP = min(V * capK, 4096)] rows) behind PSWarp, and the unchanged rescore / NMS runs on the
         pool: the views are suppressed together.  A cloud whose views yield more than capP candidates sets
         SASSD_ST_BOX_OVERFLOW.  The views are fixed here, for the life of the plan.  ValueError for a malformed spec and for
-        an inner batch the sparse index space cannot hold, before anything is allocated."""
+        an inner batch the sparse index space cannot hold, before anything is allocated.
+        fuse_iou: None (default: every path makes the calls it made before) or a number inside (0, 1) (sassd.fuse;
+        include/sassd.h "Box fusion").  post() then launches sassd_box_fuse behind rescore / NMS, one kernel: every detection
+        becomes the score-weighted mean of the candidates of its label -- of `pool` under tta, of `df` otherwise -- whose
+        rotated BEV IoU with it is at least fuse_iou.  The fused boxes are `fused` [b_user, capD, 7]; `out` is what leaves the
+        plan -- `det` with those boxes, scores / labels / counts shared -- and what results(), the frame record and the
+        annotations read, and what run_* return.  `det` keeps the unfused boxes for inspection.  ValueError for a value outside
+        (0, 1)."""
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32' or 'bf16', got %r" % (precision,))
         if sparse_precision not in ("fp32", "bf16"):
@@ -139,6 +148,7 @@ class InferencePlan:
         # b_user: the clouds per frame and the result sets per frame (the outer batch).  B: the samples the detector runs
         # on (the inner batch), b_user * V under test-time augmentation and b_user otherwise
         self.tta = None if tta is None else check_views(tta)
+        self.fuse_iou = check_fuse_iou(fuse_iou)
         self.V = 1 if self.tta is None else len(self.tta)
         self.b_user = int(batch_size)
         if self.tta is not None:
@@ -260,6 +270,11 @@ class InferencePlan:
                              counts=z(bu, dt=i32))
         self.det = dict(boxes=z(bu, self.capD, 7), scores=z(bu, self.capD), labels=z(bu, self.capD, dt=i32),
                         counts=z(bu, dt=i32))
+        # box fusion: the boxes that leave the plan are a buffer of their own; without it `out` IS `det`
+        self.fused, self.out = None, self.det
+        if self.fuse_iou is not None:
+            self.fused = z(bu, self.capD, 7)
+            self.out = dict(self.det, boxes=self.fused)
         self.middle = {}
         # all seven rulebooks through the fused pyramid (1 fill + 8 launches); the per-op chain (30) stays selectable for A/B
         self.pyr = None
@@ -702,6 +717,9 @@ class InferencePlan:
             logits = cand["logits"]
         K.rescore_nms(cand["guided"], logits, cand["labels"], cand["counts"], self.score_thr,
                       self.iou_thr, self.capD, self.det, self.status)
+        if self.fuse_iou is not None:   # the candidates NMS dropped move the box that stood for them
+            K.box_fuse(cand["guided"], logits, cand["labels"], cand["counts"], self.score_thr, self.fuse_iou, self.det,
+                       out=self.fused)
         self._seg("post", e0)
 
     def sparse_work(self):
@@ -739,7 +757,7 @@ class InferencePlan:
         else:
             self.anchor_masks(anchors_mask)
         self.post()
-        return self.det
+        return self.out
 
     def _view_clouds(self, clouds):
         """The inner batch of an eager frame: every cloud followed by its views 1 .. V-1 (sassd_tta_views_dev)."""
@@ -890,9 +908,9 @@ class InferencePlan:
                 elif self.overlap:
                     torch.cuda.current_stream(self.dev).wait_event(self.mask_ev)      # join the side stream
                 if annos:
-                    K.frame_seal_kitti(self.det, self._seq, self.status, self.calib, self.record)
+                    K.frame_seal_kitti(self.out, self._seq, self.status, self.calib, self.record)
                 elif seal:
-                    K.frame_seal(self.det, self._seq, self.status, self.record)
+                    K.frame_seal(self.out, self._seq, self.status, self.record)
 
         # capture needs a non-default stream (the legacy null stream cannot be captured)
         cap = torch.cuda.Stream(device=dev)
@@ -926,12 +944,12 @@ class InferencePlan:
         if clouds is not None:
             self.stage_inputs(clouds)
         self.graph.launch()
-        return self.det
+        return self.out
 
     def results(self):
         """The only host sync of a frame: D2H of the (small) detection buffers, like
         ssd_rotate_head.py:529-531.  Returns per-sample (boxes[k,7], scores[k], labels[k]) numpy or None."""
-        counts = self.det["counts"].cpu().numpy()
+        counts = self.out["counts"].cpu().numpy()
         st = int(self.status.item())
         if st:
             raise RuntimeError("sassd pipeline status flags 0x%x (capacity overflow / hash full)" % st)
@@ -941,6 +959,6 @@ class InferencePlan:
             if k == 0:
                 out.append((None, None, None))
                 continue
-            out.append((self.det["boxes"][b, :k].cpu().numpy(), self.det["scores"][b, :k].cpu().numpy(),
-                        self.det["labels"][b, :k].cpu().numpy().astype(np.int64)))
+            out.append((self.out["boxes"][b, :k].cpu().numpy(), self.out["scores"][b, :k].cpu().numpy(),
+                        self.out["labels"][b, :k].cpu().numpy().astype(np.int64)))
         return out

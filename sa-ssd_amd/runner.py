@@ -59,7 +59,7 @@ def train_model(model, optimizer, train_loader, lr_scheduler, sync, start_epoch,
 
 
 def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=None, world=None, inflight=0,
-                points_cap=None, raw_prefix=None, device_annos=False, ndim=4, tta=None):
+                points_cap=None, raw_prefix=None, device_annos=False, ndim=4, tta=None, fuse_iou=None):
     """Run the detector over `dataset` (test mode) -> list of KITTI result annotations in dataset order on every rank
     (this rank's frames are computed here, the others' gathered from their ranks).  `saveto`: also write result files.
     inflight > 0: the frames' raw points go through model.frame_stream(...) with that many frames in flight (1..4) instead of
@@ -78,7 +78,10 @@ def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=N
     num_input_features = 5..8 needs at least that many).
     `tta` (with inflight > 0): a test-time augmentation spec (sassd.tta: a list of (flip, angle, scale) views, the first the
     identity) -- the stream detects on every view inside the captured frame and suppresses the views' candidates together.
-    None leaves it to the model's test_cfg['tta']."""
+    None leaves it to the model's test_cfg['tta'].
+    `fuse_iou` (with inflight > 0): box fusion behind the stream's NMS (sassd.fuse: a number inside (0, 1)) -- every detection's
+    box becomes the score-weighted mean of the candidates it suppressed, of all views under tta.  None leaves it to the
+    model's test_cfg['fuse_iou']."""
     if rank is None or world is None:
         rank, _, world = D.env_world() if D.dist.is_initialized() else (0, 0, 1)
     if class_names is not None:
@@ -88,7 +91,10 @@ def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=N
     annos = []
     with torch.no_grad():
         if inflight:
-            annos = _stream_test(model, dataset, mine, workers, inflight, points_cap, raw_prefix, device_annos, ndim, tta)
+            annos = _stream_test(model, dataset, mine, workers, inflight, points_cap, raw_prefix, device_annos, ndim, tta,
+                                 fuse_iou)
+        elif fuse_iou is not None:
+            raise ValueError("fuse_iou needs inflight > 0 (the fusion is a node of the captured frame of a FrameStream)")
         elif tta is not None:
             raise ValueError("tta needs inflight > 0 (the views are made inside the captured frame of a FrameStream)")
         elif device_annos:
@@ -108,7 +114,7 @@ def single_test(model, dataset, saveto=None, class_names=None, workers=2, rank=N
 
 
 def _stream_test(model, dataset, indices, workers, inflight, points_cap=None, raw_prefix=None, device_annos=False, ndim=4,
-                 tta=None):
+                 tta=None, fuse_iou=None):
     """single_test's frames through a FrameStream: the point files are read ahead on `workers` threads, submitted as host
     clouds, and every result becomes the annotation forward_test builds for the frame's img_meta.  `ndim`: float32 columns
     per point of the files and of the clouds load_frame returns (4: KITTI)."""
@@ -138,6 +144,7 @@ def _stream_test(model, dataset, indices, workers, inflight, points_cap=None, ra
                             **({} if raw_cap is None else dict(raw_cap=raw_cap)),
                             **(dict(annos=True) if device_annos else {}),
                             **({} if tta is None else dict(tta=tta)),
+                            **({} if fuse_iou is None else dict(fuse_iou=fuse_iou)),
                             anchors_bv=dataset.anchors_bv, voxel_size=tuple(gen.voxel_size),
                             point_cloud_range=tuple(gen.point_cloud_range), max_num_points=gen.max_num_points_per_voxel,
                             max_voxels=gen._max_voxels, anchor_area_threshold=dataset.anchor_area_threshold)

@@ -700,11 +700,21 @@ class FrameStream:
     candidates of a cloud's views together (InferencePlan(tta=...); include/sassd.h "Test-time augmentation").  submit and
     collect are unchanged: batch_size clouds in, batch_size result sets out; the views are fixed for the life of the
     stream.  Composes with raw_cap, annos, sweeps, precision and sparse_precision: the views are made from the cropped /
-    merged cloud.  A malformed spec raises ValueError here, before anything is allocated."""
+    merged cloud.  A malformed spec raises ValueError here, before anything is allocated.
+
+    Box fusion: FrameStream(..., fuse_iou=0.7) ends every frame's rescore / NMS with sassd_box_fuse (InferencePlan(fuse_iou=...);
+    include/sassd.h "Box fusion"; sassd.fuse): the boxes of the record and of the annotations are the score-weighted means of
+    the candidates each detection stands for -- of all views under tta -- while scores, labels, counts and order are those of
+    the stream without it.  None (default) leaves the frame as it was.  Composes with tta, raw_cap, annos, sweeps, precision
+    and sparse_precision.  A value outside (0, 1) raises ValueError here, before anything is allocated."""
 
     def __init__(self, state_dict, inflight=3, points_cap=None, batch_size=1, anchors=None, device=None, ndim=4,
-                 raw_cap=None, annos=False, sweeps=None, sweep_cap=None, time_feature=True, tta=None, **plan_kwargs):
+                 raw_cap=None, annos=False, sweeps=None, sweep_cap=None, time_feature=True, tta=None, fuse_iou=None,
+                 **plan_kwargs):
         from .pipeline import InferencePlan, input_features_of
+        if fuse_iou is not None:
+            from .fuse import check_fuse_iou
+            fuse_iou = check_fuse_iou(fuse_iou)
         cin = input_features_of(state_dict)
         if tta is not None:
             from .tta import check_views
@@ -734,7 +744,8 @@ class FrameStream:
         self.raw_cap = None if raw_cap is None else int(raw_cap)
         self.annos = bool(annos)
         self.plans = [InferencePlan(state_dict, batch_size=batch_size, anchors=anchors, device=device,
-                                    overlap=inflight == 1, **({} if tta is None else dict(tta=tta)), **plan_kwargs)
+                                    overlap=inflight == 1, **({} if tta is None else dict(tta=tta)),
+                                    **({} if fuse_iou is None else dict(fuse_iou=fuse_iou)), **plan_kwargs)
                       for _ in range(inflight)]
         B, capD = self.plans[0].b_user, self.plans[0].capD
         self.sweeps = None if sweeps is None else int(sweeps)
