@@ -804,6 +804,64 @@ int sassd_box_fuse(const float *guided, const float *logits, const int32_t *labe
 int sassd_candidate_scores(const float *logits, long long n, float *scores, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Tracking (opt-in): identity across the frames of a stream.  A greedy centre-distance tracker of the CenterPoint kind
+ * runs as ONE kernel per frame behind the frame's detections; the tracks of every sample live in device memory between
+ * the calls.  (The reference detects on single frames and has no counterpart.)
+ *
+ * CONTRACT  (the rule is csrc/track_core.h; its numpy statement is sassd.track.track_host)
+ *   state      per sample `cap` slots (1..1024) of SASSD_TRACK_SLOT_WORDS = 14 32-bit words -- id i32 (-1: free) | label i32
+ *              | box[7] f32 | vel[2] f32 (m/s, sensor frame) | hits i32 | misses i32 | score f32 -- as slots [B,cap,14], and
+ *              next_id [B] i32.  The caller owns both and hands them to every call; ids are never reused, not even after
+ *              a reset, as long as next_id is kept.
+ *   descriptor one per sample and frame, made on the host (120 bytes, 8-byte aligned): T[3,4] f64, the transform of the
+ *              previous sensor frame into the current one (exactly [I|0] without ego motion); dyaw f64 = atan2(T[1,0],
+ *              T[0,0]) (exactly 0.0 for the identity); dt f64 = time_now - time_prev; flags i32, bit 0: reset; one pad word.
+ *   inputs     the detection buffers a frame leaves behind: det_boxes [B,capD,7] f32, det_scores [B,capD] f32, det_labels
+ *              [B,capD] i32, det_counts [B] i32, and the words at `seq` and `status`.
+ *   arithmetic float64 on the float32 fields, every product, quotient and sum rounded on its own (no fused multiply-add),
+ *              results stored as float32.
+ *   1 reset    with flag bit 0 every slot's id becomes -1.
+ *   2 predict  every live slot: px = x + vx * dt, py = y + vy * dt, pz = z;  x' = f32(((T00 px + T01 py) + T02 pz) + T03), y'
+ *              and z' alike;  yaw' = f32(double(yaw) + dyaw);  v' = (f32(T00 vx + T01 vy), f32(T10 vx + T11 vy)); the sizes
+ *              stay.  When the status word is not 0 the step ENDS here: the tracks have been carried into the current sensor
+ *              frame, nothing else changes, every output row is empty and the count written is 0.
+ *   3 match    D = clamp(det_counts[b], 0, capD).  For d = 0 .. D-1 in the detector's order: slot i is eligible when its id
+ *              >= 0, it is not yet matched in this frame, its label equals the detection's, the label lies in [0, n_labels)
+ *              and c_i = dx * dx + dy * dy <= double(max_dist[label])^2 with dx = double(det.x) - double(x'_i), dy alike.  A
+ *              NaN cost is not eligible.  The match is the eligible slot of least cost, on equal cost the lowest slot.
+ *   4 update   a matched slot: g = 1 when hits == 1, else alpha.  When dt is finite and > 0: vx = f32(double(vx') + g *
+ *              ((double(det.x) - double(x')) / dt)), vy alike; otherwise the velocity stays v'.  The box and the score become
+ *              the detection's, bit for bit; hits = min(hits + 1, 1 << 30), misses = 0.
+ *   5 age      every live slot that was not matched: misses += 1, and id = -1 when misses > max_age.
+ *   6 births   every unmatched detection with score >= birth_score, in order, takes the lowest free slot (slots freed in
+ *              step 5 count): id = next_id++, the detection's box, label and score, vel = 0, hits = 1, misses = 0.  When no
+ *              slot is free the detection keeps id -1 and the sample's `dropped` goes up by one.
+ *   record     32-bit words, SASSD_TRACK_HEADER_WORDS = 8 in front: SASSD_TRACK_MAGIC, the word at `seq`, the status word
+ *              seen, B, capD, cap, 0, 0; then count [B] (the D used), dropped [B], next_id [B], det_id [B,capD] i32, det_hits
+ *              [B,capD] i32, det_vel [B,capD,2] f32, and the whole slot table [B,cap,14] after the step.  A detection's
+ *              values are those of its slot after the step; rows at and past D, and detections without a track, hold
+ *              -1 / 0 / (0, 0).  sassd.track.track_record_layout is the Python statement of these offsets.
+ *   launches   one kernel, no workspace: B workgroups of 256 threads, the sample's table in LDS, the detections staged there 64
+ *              at a time.  Per detection a block arg-min: per-thread scan, wave64 shuffle reduction, the four waves through
+ *              LDS, one barrier.  Births by two
+ *              block scans.  No host sync, no allocation, no memset, no atomics, no workgroup waits for another.
+ *   errors     SASSD_EINVAL before any HIP call: a NULL or misaligned pointer (4 bytes; desc 8), batch / capD / cap < 1,
+ *              batch > 65535, capD > 16384, cap > 1024, n_labels outside 1..8, alpha outside (0, 1], a max_dist that is
+ *              negative or not finite, a negative max_age, a NaN birth_score.  SASSD_ENOSPC: record_bytes below
+ *              sassd_track_record_bytes(batch, capD, cap) (0 for shapes the step refuses).  max_dist is a HOST array of
+ *              n_labels floats.
+ * ---------------------------------------------------------------------------------------------- */
+#define SASSD_TRACK_MAGIC 0x53540001
+#define SASSD_TRACK_HEADER_WORDS 8
+#define SASSD_TRACK_SLOT_WORDS 14
+#define SASSD_TRACK_DESC_BYTES 120
+size_t sassd_track_record_bytes(int batch, int capD, int cap);
+int sassd_track_step(const float *det_boxes, const float *det_scores, const int32_t *det_labels, const int32_t *det_counts,
+                     int batch, int capD, const int32_t *seq, const int32_t *status, const void *desc, int32_t *slots,
+                     int32_t *next_id, int cap, const float *max_dist, int n_labels, int max_age, double alpha,
+                     float birth_score, void *record, size_t record_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Frame record: the LAST node of a captured frame.  sassd_frame_seal copies the detection buffers sassd_rescore_nms
  * left behind into ONE fixed-size, self-describing device record, so that a frame leaves the GPU in one asynchronous
  * copy (sassd.stream.FrameStream; the reference reads its detections with three blocking copies per sample,

@@ -52,6 +52,9 @@ _SIGS = {
     # box fusion behind rescore / NMS (include/sassd.h "Box fusion")
     "sassd_box_fuse": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _I, _P, _P]),
     "sassd_candidate_scores": (_I, [_P, C.c_longlong, _P, _P]),
+    # tracking behind a frame's detections (include/sassd.h "Tracking")
+    "sassd_track_record_bytes": (_SZ, [_I, _I, _I]),
+    "sassd_track_step": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, C.c_double, _F, _P, _SZ, _P]),
     "sassd_hash_bytes": (_SZ, [_I]),
     "sassd_hash_build": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P, _P]),
     "sassd_rulebook_subm": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P, _P]),

@@ -1275,6 +1275,53 @@ def candidate_scores(logits):
     return out
 
 
+def track_record_bytes(batch, cap_d, cap):
+    """Size of the track record of include/sassd.h ("Tracking") for `batch` samples, `cap_d` detection rows, `cap` slots."""
+    n = int(_C.lib().sassd_track_record_bytes(int(batch), int(cap_d), int(cap)))
+    if n == 0:
+        raise ValueError("no track record for batch %d x capD %d x cap %d" % (batch, cap_d, cap))
+    return n
+
+
+def track_step(det, seq, status, desc, slots, next_id, params, record):
+    """One tracker step behind a frame's detections (include/sassd.h "Tracking"; sassd.track.track_host states it): `det` --
+    dict(boxes [b, capD, 7] f32, scores [b, capD] f32, labels [b, capD] i32, counts [b] i32), e.g. rescore_nms's out dict --
+    the int32 words at `seq` and `status`, the descriptors `desc` (uint8, b * 120 bytes: sassd.track.pack_desc), the state
+    `slots` [b, cap, 14] i32 and `next_id` [b] i32 (updated in place), `params` a track spec (sassd.track.check_track) whose
+    cap is the state's, `record` a uint8 buffer of at least track_record_bytes(b, capD, cap).  `det`, `seq`, `status` and `desc`
+    are only read.  One kernel launch, no workspace; not part of a captured frame, since its state outlives the frame."""
+    import ctypes
+    from .track import check_track, DESC_BYTES, SLOT_WORDS
+    p = check_track(dict(params) if params is not None else None)
+    if p is None:
+        raise ValueError("track_step: params must be a track spec, got None")
+    boxes = det["boxes"]
+    if boxes.dim() != 3 or boxes.shape[0] < 1 or boxes.shape[1] < 1 or boxes.shape[2] != 7:
+        raise ValueError("track_step: det['boxes'] must be [b >= 1, capD >= 1, 7], got %s" % (tuple(boxes.shape),))
+    b, cap_d, cap = int(boxes.shape[0]), int(boxes.shape[1]), p["cap"]
+    for name, t, dtype, shape in (("det['boxes']", boxes, torch.float32, (b, cap_d, 7)),
+                                  ("det['scores']", det["scores"], torch.float32, (b, cap_d)),
+                                  ("det['labels']", det["labels"], torch.int32, (b, cap_d)),
+                                  ("det['counts']", det["counts"], torch.int32, (b,)),
+                                  ("seq", seq, torch.int32, (1,)), ("status", status, torch.int32, (1,)),
+                                  ("desc", desc, torch.uint8, (b * DESC_BYTES,)),
+                                  ("slots", slots, torch.int32, (b, cap, SLOT_WORDS)), ("next_id", next_id, torch.int32, (b,))):
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError("track_step: %s must be a contiguous %s %s, got %s %s" % (name, list(shape), dtype, tuple(t.shape), t.dtype))
+    need = track_record_bytes(b, cap_d, cap)
+    if record.dtype != torch.uint8 or record.dim() != 1 or record.numel() < need or not record.is_contiguous():
+        raise ValueError("track_step: record must be a contiguous uint8 buffer of at least %d bytes, got %s %s"
+                         % (need, tuple(record.shape), record.dtype))
+    _chk_cuda(boxes, det["scores"], det["labels"], det["counts"], seq, status, desc, slots, next_id, record)
+    md = (ctypes.c_float * len(p["max_dist"]))(*p["max_dist"])
+    rc = _C.lib().sassd_track_step(_C.ptr(boxes), _C.ptr(det["scores"]), _C.ptr(det["labels"]), _C.ptr(det["counts"]), b, cap_d,
+                                   _C.ptr(seq), _C.ptr(status), _C.ptr(desc), _C.ptr(slots), _C.ptr(next_id), cap, md,
+                                   len(p["max_dist"]), p["max_age"], p["alpha"], p["birth_score"], _C.ptr(record),
+                                   record.numel(), _C.stream())
+    _C.check(rc, "sassd_track_step")
+    return record
+
+
 def frame_record_bytes(batch, cap_d):
     """Size of the frame record of include/sassd.h ("Frame record") for `batch` samples of `cap_d` detection rows."""
     n = int(_C.lib().sassd_frame_record_bytes(int(batch), int(cap_d)))

@@ -409,7 +409,8 @@ class FrameRing:
         stage(seq, clouds)   check and queue the inputs of one frame (ValueError for inputs it cannot take: nothing queued);
                              called as stage(seq, clouds, frustums) when submit() was given frustums, and only then;
                              with calibs=<calibs> as a keyword when submit() was given calibs, and only then;
-                             with sweeps=<sweeps> as a keyword when submit() was given sweeps, and only then
+                             with sweeps=<sweeps> as a keyword when submit() was given sweeps, and only then;
+                             with track=<track> as a keyword when submit() was given track, and only then
         launch()             queue the frame and the copy of its record
         ready() / wait()     has the record arrived / block until it has
         record()             the arrived record, valid until the next stage()
@@ -444,7 +445,7 @@ class FrameRing:
                 recover()
         self.busy[i] = None
 
-    def submit(self, clouds, frustums=None, calibs=None, sweeps=None):
+    def submit(self, clouds, frustums=None, calibs=None, sweeps=None, track=None):
         if self.closed:
             raise RuntimeError("FrameStream is closed")
         t = self.next_ticket
@@ -455,6 +456,8 @@ class FrameRing:
         kw = {} if calibs is None else dict(calibs=calibs)
         if sweeps is not None:
             kw["sweeps"] = sweeps
+        if track is not None:
+            kw["track"] = track
         self.slots[i].stage(t & _SEQ_MASK, *args, **kw)    # a ValueError leaves the ticket unused and the slot free
         self.slots[i].launch()
         self.busy[i] = t
@@ -488,7 +491,8 @@ class FrameRing:
         """(ticket, result) per batch of `batches`, in order, with at most len(slots) frames submitted and not yet yielded.
         A batch is a list of clouds, or the tuple (clouds, frustums) for a stream with raw_cap, or the tuple
         (clouds, frustums-or-None, calibs) for a stream with annos, or the tuple
-        (clouds, frustums-or-None, calibs-or-None, sweeps) for a stream with sweeps."""
+        (clouds, frustums-or-None, calibs-or-None, sweeps) for a stream with sweeps, or the tuple
+        (clouds, frustums-or-None, calibs-or-None, None, track) for a tracking stream without sweeps."""
         pending = deque()
         try:
             batches = iter(batches)
@@ -500,7 +504,7 @@ class FrameRing:
                     clouds = next(batches)
                 except StopIteration:
                     break
-                if isinstance(clouds, tuple):           # (clouds, frustums[, calibs[, sweeps]]): a raw / annos / sweeps batch
+                if isinstance(clouds, tuple):           # (clouds, frustums[, calibs[, sweeps[, track]]])
                     pending.append(self.submit(*clouds))
                 else:
                     pending.append(self.submit(clouds))
@@ -533,9 +537,12 @@ class _PlanSlot:
     With `sweeps` -- dict(book=<SweepBook>, ring=<[B,R,sweep_cap,ndim] f32 device>, events=<one per ring slot>,
     time_feature=), shared by the stream's slots -- `ndim` is the width of a submitted sweep, the pinned clouds are
     [B x sweep_cap x ndim f32] and go into the ring slot the book names; the plan's first node merges the ring slots of
-    the frame's descriptors into plan.pts_in (ndim + time_feature columns)."""
+    the frame's descriptors into plan.pts_in (ndim + time_feature columns).
+    With `track` -- dict(tracker=<sassd.track.Tracker>, book=<TrackBook>, events=<one per slot>, last=<the slot index of the
+    previous ticket or None>), shared by the stream's slots -- the slot owns a pinned descriptor block, a device and a pinned
+    track record, and launch() queues the tracker behind the frame (FrameStream, "Tracking")."""
 
-    def __init__(self, plan, points_cap, ndim, raw_cap=None, annos=False, sweeps=None):
+    def __init__(self, plan, points_cap, ndim, raw_cap=None, annos=False, sweeps=None, track=None, index=0):
         import torch
         self.torch, self.plan = torch, plan
         dev, B = plan.dev, plan.b_user               # the clouds of a frame (a plan with tta runs more samples inside)
@@ -564,16 +571,31 @@ class _PlanSlot:
         self.np_pts, self.np_rec = self.pin_pts.numpy(), self.pin_rec.numpy()
         self.event = torch.cuda.Event()
         self.feed = torch.cuda.Event()          # orders device-tensor clouds (produced on the caller's stream) before their copy
+        self.trk, self.index = track, int(index)
+        if track is not None:
+            from .track import DESC_BYTES
+            tracker = track["tracker"]
+            self.pin_desc = torch.zeros(B * DESC_BYTES, dtype=torch.uint8).pin_memory()
+            self.np_desc = self.pin_desc.numpy()
+            self.dev_trk = tracker.new_record()     # the slot's own: the next ticket's step may run while this one is copied
+            self.pin_trk = torch.zeros(tracker.record_bytes, dtype=torch.uint8).pin_memory()
+            self.np_trk = self.pin_trk.numpy()
 
-    def stage(self, seq, clouds, frustums=None, calibs=None, sweeps=None):
+    def stage(self, seq, clouds, frustums=None, calibs=None, sweeps=None, track=None):
         torch, plan = self.torch, self.plan
         view = self.np_stage
+        tplan = None
+        if self.trk is not None or track is not None:
+            from .track import track_items
+            titems = track_items(self.trk is not None, self.sw is not None, sweeps, track)
         if self.sw is None:
             if sweeps is not None:
                 raise ValueError("sweeps given to a stream built without sweeps= (its clouds are taken as they are)")
             checked = check_frame_inputs(clouds, frustums, plan.b_user, self.ndim, self.cap, self.raw_cap, calibs,
                                          self.annos)                                         # nothing is queued before this
             planes, calib = checked if self.annos else (checked, None)
+            if self.trk is not None:
+                tplan = self.trk["book"].plan(titems)                                        # the book is unchanged
             dev_pts = self.dev_pts
         else:
             if frustums is not None:
@@ -581,11 +603,17 @@ class _PlanSlot:
             book = self.sw["book"]
             d = book.plan(clouds, sweeps)                                                    # nothing is queued before this,
             planes, calib = None, _check_calibs(calibs, None, plan.b_user, self.annos)            # and the book is unchanged
+            if self.trk is not None:
+                tplan = self.trk["book"].plan(titems)
             assert (d["k"] + 1) & _SEQ_MASK == seq      # ticket t carries sweep t - 1: frame t - inflight, the last reader of
             book.commit(d)                              # the ring slot written now, ran on this slot's stream
             for key in ("slot", "count", "xform", "T", "dt"):
                 view["sweep_" + key][...] = d[key]
             dev_pts = [self.sw["ring"][b, d["write"]] for b in range(plan.b_user)]
+        if tplan is not None:                           # every check has passed: the submit is accepted
+            from .track import pack_desc
+            self.trk["book"].commit(tplan)
+            self.np_desc[...] = pack_desc(tplan)
         if planes is not None:
             view["planes"][...] = planes
         if calib is not None:
@@ -620,7 +648,21 @@ class _PlanSlot:
         with torch.cuda.stream(self.stream):
             self.plan.graph.launch()
             self.pin_rec.copy_(self.plan.record, non_blocking=True)
-            self.event.record(self.stream)
+            if self.trk is not None:
+                self._launch_tracker()
+            self.event.record(self.stream)              # last: it covers both records
+
+    def _launch_tracker(self):
+        """Behind the frame, on the slot's stream (the caller has made it current): wait for the previous ticket's step --
+        it ran on another slot's stream when inflight > 1 --, copy the descriptors, step the stream's tracker on this plan's
+        detections and status word, record the slot's track event, copy the record out."""
+        trk, plan = self.trk, self.plan
+        if trk["last"] is not None and trk["last"] != self.index:
+            self.stream.wait_event(trk["events"][trk["last"]])
+        trk["tracker"].step(plan.out, plan.status, self.pin_desc, seq=plan._seq, record=self.dev_trk)
+        trk["events"][self.index].record(self.stream)
+        trk["last"] = self.index
+        self.pin_trk.copy_(self.dev_trk, non_blocking=True)
 
     def ready(self):
         return self.event.query()
@@ -629,7 +671,7 @@ class _PlanSlot:
         self.event.synchronize()
 
     def record(self):
-        return self.np_rec
+        return self.np_rec if self.trk is None else (self.np_rec, self.np_trk)
 
     def recover(self):
         """InferencePlan's status word is sticky and the plan, its kernels and the seal leave it so.  The STREAM clears it, and
@@ -706,12 +748,35 @@ class FrameStream:
     include/sassd.h "Box fusion"; sassd.fuse): the boxes of the record and of the annotations are the score-weighted means of
     the candidates each detection stands for -- of all views under tta -- while scores, labels, counts and order are those of
     the stream without it.  None (default) leaves the frame as it was.  Composes with tta, raw_cap, annos, sweeps, precision
-    and sparse_precision.  A value outside (0, 1) raises ValueError here, before anything is allocated."""
+    and sparse_precision.  A value outside (0, 1) raises ValueError here, before anything is allocated.
+
+    Tracking: FrameStream(..., track=dict(max_dist=2.0 | one per label, max_age=3, alpha=0.5, cap=256, birth_score=0.0)) keeps
+    the tracks of every sample in device memory for the life of the stream and steps them behind every frame with ONE kernel,
+    sassd_track_step (include/sassd.h "Tracking"; sassd.track.track_host states it): greedy centre-distance association in the
+    detector's order, a velocity per track, tracks that coast for up to max_age frames.  The kernel is launched OUTSIDE the
+    captured graph, on the slot's stream behind graph.launch(), because its state is shared between the plans; it reads that
+    plan's `out` and `status`.  Order per ticket: wait on the track event of the previous ticket (another slot's stream when
+    inflight > 1), copy the descriptors, step, record the slot's track event, copy the track record to a pinned buffer; the
+    slot's completion event comes last and covers both records.  Pose and time: on a stream with sweeps= those of the sweep
+    dicts, `first` included -- nothing new is passed; on any other stream submit(clouds, ..., track=[dict(time=<seconds>,
+    pose=<4x4 f64 sensor-to-world or None>, first=<bool>), ...]), one per cloud.  The host keeps the previous pose and time per
+    sample (sassd.track.TrackBook) and commits them only when the submit is accepted; a sample's first frame and a frame with
+    first=True reset its tracks (ids are never reused).  collect() appends one element per sample, trk = dict(ids, vel, hits,
+    dropped, coast=dict(ids, labels, boxes, vel, misses, scores)): ids / vel / hits per detection, `coast` the tracks alive but
+    not seen in this frame, at their predicted places; everything before it is byte for byte what the stream without track=
+    returns.  A frame whose status word is not zero raises from its collect() as ever; its step only carried the tracks into
+    its sensor frame.  A missing or miscounted track=, a non-finite time, a pose that is not a finite 4x4 matrix, track= next
+    to sweeps=, and track= given to a stream built without it raise ValueError at submit, before anything is queued and with
+    the book unchanged.  Composes with raw_cap, annos, sweeps, tta, fuse_iou and the precisions: the tracker reads whatever
+    plan.out is.  A malformed spec raises ValueError here, before anything is allocated."""
 
     def __init__(self, state_dict, inflight=3, points_cap=None, batch_size=1, anchors=None, device=None, ndim=4,
                  raw_cap=None, annos=False, sweeps=None, sweep_cap=None, time_feature=True, tta=None, fuse_iou=None,
-                 **plan_kwargs):
+                 track=None, **plan_kwargs):
         from .pipeline import InferencePlan, input_features_of
+        if track is not None:
+            from .track import check_track
+            track = check_track(track)
         if fuse_iou is not None:
             from .fuse import check_fuse_iou
             fuse_iou = check_fuse_iou(fuse_iou)
@@ -758,13 +823,32 @@ class FrameStream:
             self._book = SweepBook(B, self.sweeps, R, self.sweep_cap, ndim, inflight)
             extra["sweeps"] = dict(book=self._book, ring=self.sweep_ring, time_feature=self.time_feature,
                                    events=[torch.cuda.Event() for _ in range(R)])
-        self._slots = [_PlanSlot(p, self.points_cap, ndim, self.raw_cap, self.annos, **extra) for p in self.plans]
-        self._ring = FrameRing(self._slots, lambda rec, seq: decode_record(rec, B, capD, seq, self.annos))
+        self.track = track
+        if track is None:
+            self._slots = [_PlanSlot(p, self.points_cap, ndim, self.raw_cap, self.annos, **extra) for p in self.plans]
+            self._ring = FrameRing(self._slots, lambda rec, seq: decode_record(rec, B, capD, seq, self.annos))
+            return
+        import torch
+        from .track import Tracker, TrackBook, decode_track_record, results_of
+        self.tracker = Tracker(B, capD, self.plans[0].dev, **track)
+        self._track_book = TrackBook(B)
+        extra["track"] = dict(tracker=self.tracker, book=self._track_book, last=None,
+                              events=[torch.cuda.Event() for _ in range(inflight)])
+        self._slots = [_PlanSlot(p, self.points_cap, ndim, self.raw_cap, self.annos, index=i, **extra)
+                       for i, p in enumerate(self.plans)]
+        cap = self.tracker.cap
 
-    def submit(self, clouds, frustums=None, calibs=None, sweeps=None):
-        if sweeps is not None:
-            return self._ring.submit(clouds, frustums, calibs, sweeps=sweeps)
-        return self._ring.submit(clouds, frustums, calibs)
+        def decode(rec, seq):
+            dets = decode_record(rec[0], B, capD, seq, self.annos)      # raises the frame's status error
+            trk = decode_track_record(rec[1], B, capD, cap, seq)
+            return [tuple(d) + (results_of(trk, b),) for b, d in enumerate(dets)]
+        self._ring = FrameRing(self._slots, decode)
+
+    def submit(self, clouds, frustums=None, calibs=None, sweeps=None, track=None):
+        kw = {} if sweeps is None else dict(sweeps=sweeps)
+        if track is not None:
+            kw["track"] = track
+        return self._ring.submit(clouds, frustums, calibs, **kw)
 
     def collect(self, ticket):
         return self._ring.collect(ticket)
